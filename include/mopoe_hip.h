@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPOE_ABI_VERSION 19
+#define MOPOE_ABI_VERSION 20
 
 /* error codes */
 #define MOPOE_OK 0
@@ -253,6 +253,46 @@ int mopoe_latent_bwd(const float* const mu_in[3], const float* const lv_in[3], c
                      const float* g_joint_lv, const float* g_z, const float* g_klds,
                      const float* g_joint_div, float* const d_mu_in[3], float* const d_lv_in[3],
                      void* stream);
+
+/* ---- latent space of the mixture-of-experts methods -------------------------------------------------
+ * method MOPOE_LATENT_MOE (the MMVAE baseline) or MOPOE_LATENT_JSD (mixture of experts with a dynamic prior): one
+ * kernel for BaseMMVae.inference with moe_fusion (mimic/utils/BaseMMVae.py:101-111,139-196),
+ * utils.mixture_component_selection (utils/utils.py:55-77), divergence_static_prior / divergence_dynamic_prior
+ * (BaseMMVae.py:71-99) with calc_group_divergence_moe / calc_alphaJSD_modalities / alpha_poe
+ * (evaluation/divergence_measures/mm_div.py:20-32,67-106, kl_div.py:8-16), losses.calc_klds
+ * (evaluation/losses.py:24-31) and utils.reparameterize (utils/utils.py:45-48).
+ *   mu_in/lv_in[3]: as mopoe_latent_fwd; n = number of present modalities, K = number of subsets.
+ *   C = n (moe) or n + 1 (jsd) components: the present singletons in the order PA, Lateral, text, then for jsd the
+ *       N(0,I) prior component (mu 0, logvar 0).
+ *   member_row_start[3][4]: HOST array, row partition of a subset of m = 1, 2, 3 members (row m-1 holds its m+1 starts,
+ *       the rest is ignored); member j in sorted-name order (Lateral, PA, text) gives the subset's rows
+ *       [member_row_start[m-1][j], member_row_start[m-1][j+1]) as an exact copy.
+ *   comp_row_start[C+1]: HOST array, the joint's partition over the components.  w[C]: HOST array of the joint
+ *       divergence weights (moe: the re-normalised 1/n; jsd: the alpha = 1/(n+1) of the dynamic prior as well).
+ *   outputs: sub_mu/sub_lv [K,B,D]; comp_mu/comp_lv [C,B,D]; joint_mu/joint_lv/z [B,D]; klds [K] = KL(subset_k ||
+ *       N(0,I)) / norm; individual_divs [C] = KL(component_c || prior) / norm, the prior being N(0,I) (moe) or the
+ *       dynamic prior N(pd_mu, exp(pd_lv)) (jsd); joint_div [1] = sum_c w[c]*individual_divs[c]; pd_mu/pd_lv [B,D]
+ *       (jsd only; may be NULL for moe).  ws: double[16] workspace that must be zero on entry and is left zero. */
+#define MOPOE_LATENT_MOE 0
+#define MOPOE_LATENT_JSD 1
+int mopoe_latent_mixture_fwd(int32_t method, const float* const mu_in[3], const float* const lv_in[3],
+                             const float* eps, int32_t B, int32_t D, const int32_t* member_row_start,
+                             const int32_t* comp_row_start, const float* w, float norm, float* sub_mu,
+                             float* sub_lv, float* comp_mu, float* comp_lv, float* joint_mu, float* joint_lv,
+                             float* z, float* klds, float* individual_divs, float* joint_div, float* pd_mu,
+                             float* pd_lv, double* ws, void* stream);
+
+/* backward: every g_* may be NULL (g_pd_mu/g_pd_lv are read for jsd only).  No gradient flows from the prior
+ * component of jsd; the dynamic prior's gradient reaches every component it was made of.
+ * d_mu_in/d_lv_in[3] are overwritten for present modalities. */
+int mopoe_latent_mixture_bwd(int32_t method, const float* const mu_in[3], const float* const lv_in[3],
+                             const float* eps, int32_t B, int32_t D, const int32_t* member_row_start,
+                             const int32_t* comp_row_start, const float* w, float norm, const float* g_sub_mu,
+                             const float* g_sub_lv, const float* g_comp_mu, const float* g_comp_lv,
+                             const float* g_joint_mu, const float* g_joint_lv, const float* g_z,
+                             const float* g_klds, const float* g_individual_divs, const float* g_joint_div,
+                             const float* g_pd_mu, const float* g_pd_lv, float* const d_mu_in[3],
+                             float* const d_lv_in[3], void* stream);
 
 /* ---- likelihoods -----------------------------------------------------------------------------------
  * Laplace(loc = x_hat, scale): out[0] = -sum log p(x | x_hat) / norm

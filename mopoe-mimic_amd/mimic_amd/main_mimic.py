@@ -123,7 +123,7 @@ class Main:
 def parse_flags(argv=None) -> argparse.Namespace:
     from .utils.experiment import default_flags
     base = default_flags(device=None)
-    ap = argparse.ArgumentParser(description="MoPoE joint-ELBO training on MI355X (hot-path launcher)")
+    ap = argparse.ArgumentParser(description="MoPoE / MMVAE / JSD training on MI355X (hot-path launcher; --method)")
     for k, v in sorted(vars(base).items()):
         if isinstance(v, bool):
             ap.add_argument(f"--{k}", type=lambda x: str(x).lower() in ("1", "true", "yes"), default=v)
@@ -134,7 +134,8 @@ def parse_flags(argv=None) -> argparse.Namespace:
     base.__dict__.update(vars(ns))
     base.alpha_modalities = [base.div_weight_uniform_content, base.div_weight_m1_content, base.div_weight_m2_content,
                              base.div_weight_m3_content]
-    return base
+    from .utils.filehandling import get_method
+    return get_method(base)   # (--method picks the objective, as mimic/main_mimic.py does through get_method)
 
 
 if __name__ == "__main__":

@@ -1,9 +1,11 @@
 """MoPoE model: encoders -> fused latent kernel -> decoders.
 
 API of the reference's ``BaseMMVae`` (mimic/utils/BaseMMVae.py:16-231) and ``VAEtrimodalMimic``
-(mimic/networks/VAEtrimodalMimic.py:12-163) for ``method='joint_elbo'``; results-dict schema as in
-SURVEY.md §8(a3,a7).  The 7-subset Python loop, the PoE, the mixture selection, both KL passes and the
-reparameterisation of the reference are ONE kernel here (ops.latent_fwd) and one autograd node.
+(mimic/networks/VAEtrimodalMimic.py:12-163) for ``method`` 'joint_elbo' (MoPoE), 'moe' (the MMVAE baseline) and 'jsd'
+(mixture of experts with a dynamic prior); results-dict schema as in SURVEY.md §8(a3,a7).  The 7-subset Python loop, the
+fusion (PoE for joint_elbo, mixture selection for moe/jsd), the joint mixture selection, the KL passes (and the dynamic
+prior of jsd) and the reparameterisation of the reference are ONE kernel here (ops.latent_fwd, ops.latent_mixture_fwd)
+and one autograd node.  'poe' (the MVAE baseline) has no path: the reference cannot train it (set_fusion_functions).
 """
 from __future__ import annotations
 
@@ -90,6 +92,35 @@ class _LatentFuse(torch.autograd.Function):
         return (None, None, None, None, None, *grads)
 
 
+class _LatentMixture(torch.autograd.Function):
+    """method 'moe' / 'jsd': (mu, logvar) of the present modalities + eps -> subset (mu, logvar) [K,B,D], component
+    (mu, logvar) [C,B,D], joint (mu, logvar), z, klds [K], individual_divs [C], joint_divergence (+ the dynamic prior's
+    (mu, logvar) for jsd)."""
+
+    @staticmethod
+    def forward(ctx, method, present, member_rs, comp_rs, w, norm, eps, *enc):
+        mu_in, lv_in, j = [None] * 3, [None] * 3, 0
+        for slot in range(3):
+            if present[slot]:
+                mu_in[slot], lv_in[slot] = enc[j].contiguous(), enc[j + 1].contiguous()
+                j += 2
+        outs = ops.latent_mixture_fwd(method, mu_in, lv_in, eps, member_rs, comp_rs, w, norm)
+        ctx.args = (method, mu_in, lv_in, eps, member_rs, comp_rs, w, norm, present)
+        ctx.set_materialize_grads(False)
+        return outs if method == "jsd" else outs[:10]   # (no dynamic prior for moe)
+
+    @staticmethod
+    def backward(ctx, *g):
+        method, mu_in, lv_in, eps, member_rs, comp_rs, w, norm, present = ctx.args
+        g = [None if t is None else t.contiguous() for t in g] + [None] * (12 - len(g))
+        dmu, dlv = ops.latent_mixture_bwd(method, mu_in, lv_in, eps, member_rs, comp_rs, w, norm, *g)
+        grads = []
+        for slot in range(3):
+            if present[slot]:
+                grads += [dmu[slot], dlv[slot]]
+        return (None, None, None, None, None, None, None, *grads)
+
+
 class BaseMMVae(ABC, nn.Module):
     def __init__(self, flags, modalities, subsets):
         super().__init__()
@@ -109,9 +140,23 @@ class BaseMMVae(ABC, nn.Module):
         ...
 
     def set_fusion_functions(self):
-        if not getattr(self.flags, "joint_elbo", False) or self.flags.modality_moe or self.flags.modality_jsd \
-                or self.flags.modality_poe:
-            raise NotImplementedError("only method='joint_elbo' (MoPoE) has a HIP path (SURVEY §2.1-3)")
+        """BaseMMVae.py:51-69, in its order of precedence: moe, jsd, poe, joint_elbo (utils.filehandling.get_method sets
+        the one flag of a method).  self.method names the latent kernel the model runs."""
+        f = self.flags
+        if getattr(f, "modality_moe", False):
+            self.method = "moe"
+        elif getattr(f, "modality_jsd", False):
+            self.method = "jsd"
+        elif getattr(f, "modality_poe", False):
+            raise NotImplementedError(
+                "method='poe' (MVAE) has no HIP path: the reference cannot train it either -- calc_poe_loss "
+                "(mimic/evaluation/losses.py:66) calls the model with a one-modality dict, and VAEtrimodalMimic.forward "
+                "then indexes input_batch for all three modalities (mimic/networks/VAEtrimodalMimic.py:46): KeyError")
+        elif getattr(f, "joint_elbo", False):
+            self.method = "joint_elbo"
+        else:
+            raise NotImplementedError("no method selected: set flags.method to 'joint_elbo', 'moe' or 'jsd' and apply "
+                                      "utils.filehandling.get_method")
         w = reweight_weights(torch.Tensor(self.flags.alpha_modalities))
         self.weights = w.to(self.flags.device)
 
@@ -130,12 +175,14 @@ class BaseMMVae(ABC, nn.Module):
         k = len(active)
         first = enc_mods[[n for n, p in zip(("PA", "Lateral", "text"), present) if p][0]][0]
         b, d = first.shape
-        row_start = mixture_row_starts(b, k)
         enc_flat = []
         for name, p in zip(("PA", "Lateral", "text"), present):
             if p:
                 enc_flat += [enc_mods[name][0], enc_mods[name][1]]
         eps = self._draw_eps(b, d, first.device)
+        if self.method != "joint_elbo":
+            return self._mixture_inference(latents, present, active, enc_flat, eps, first)
+        row_start = mixture_row_starts(b, k)
         mus, lvs, jm, jl, z, klds, jd = _LatentFuse.apply(present, row_start, kl_weights(k),
                                                           float(self.flags.batch_size), eps, *enc_flat)
         latents["mus"], latents["logvars"] = mus, lvs
@@ -145,6 +192,31 @@ class BaseMMVae(ABC, nn.Module):
         # by-products of the fused kernel, consumed by forward() / losses.calc_klds
         latents["_z"], latents["_klds"], latents["_joint_divergence"] = z, klds, jd
         latents["_subset_order"] = [key for key, _m in active]
+        return latents
+
+    def _mixture_inference(self, latents, present, active, enc_flat, eps, first):
+        """moe / jsd (BaseMMVae.py:139-196 with moe_fusion): every subset is a mixture selection of its members' rows,
+        the components are the singletons (+ the N(0,I) prior for jsd, BaseMMVae.py:178-184, built with the ACTUAL
+        batch size where the reference uses flags.batch_size), the joint is a mixture selection over the components."""
+        b = first.shape[0]
+        n = sum(present)
+        c = n + (self.method == "jsd")
+        # subset members and components carry weights 1/m re-normalised (moe_fusion): the floor(B*w) partitions
+        member_rs = [mixture_row_starts(b, m) for m in (1, 2, 3)]
+        # joint divergence weights: divergence_static_prior re-normalises 1/n (moe); calc_alphaJSD_modalities takes the
+        # alphas 1/(n+1) as they are (jsd)
+        w = kl_weights(n) if self.method == "moe" else [float(torch.tensor(1 / float(c)))] * c
+        outs = _LatentMixture.apply(self.method, present, member_rs, mixture_row_starts(b, c), w,
+                                    float(self.flags.batch_size), eps, *enc_flat)
+        sub_mu, sub_lv, comp_mu, comp_lv, jm, jl, z, klds, indiv, jd = outs[:10]
+        latents["mus"], latents["logvars"] = comp_mu, comp_lv
+        latents["weights"] = (1 / float(c)) * torch.ones(c, device=first.device)
+        latents["joint"] = [jm, jl]
+        latents["subsets"] = {key: [sub_mu[i], sub_lv[i]] for i, (key, _m) in enumerate(active)}
+        latents["_z"], latents["_klds"], latents["_joint_divergence"] = z, klds, jd
+        latents["_subset_order"] = [key for key, _m in active]
+        latents["_individual_divs"] = indiv
+        latents["_dyn_prior"] = list(outs[10:12]) if self.method == "jsd" else None
         return latents
 
     def generate(self, num_samples=None):
@@ -196,7 +268,8 @@ class VAEtrimodalMimic(BaseMMVae, nn.Module):
         latents = self.inference(input_batch)
         results = {"latents": latents, "group_distr": latents["joint"],
                    "joint_divergence": latents["_joint_divergence"].view(()),
-                   "individual_divs": latents["_klds"], "dyn_prior": None}
+                   "individual_divs": latents.get("_individual_divs", latents["_klds"]),
+                   "dyn_prior": latents.get("_dyn_prior")}
         z = latents["_z"]
         # the decoders are independent: one grouped autograd node, each network on its modality's stream (nets.run_group)
         items = [(m_key, net, (None, z))

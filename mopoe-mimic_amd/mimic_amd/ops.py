@@ -20,7 +20,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOPOE_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libmopoe_hip.so")  # env override: A/B builds
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 RES_A, RES_B = 2.0, 0.3
 BN_EPS = 1e-5
@@ -976,6 +976,67 @@ def latent_bwd(mu_in, lv_in, eps, row_start, w, norm, g_mus, g_lvs, g_jm, g_jl, 
     _check(lib().mopoe_latent_bwd(_ptr3(mu_in), _ptr3(lv_in), _p(eps), b, d, rs, wa, C.c_float(norm), _p(g_mus),
                                   _p(g_lvs), _p(g_jm), _p(g_jl), _p(g_z), _p(g_klds), _p(g_jd), _ptr3(dmu),
                                   _ptr3(dlv), _stream()))
+    return dmu, dlv
+
+
+LATENT_METHODS = {"moe": 0, "jsd": 1}   # MOPOE_LATENT_MOE / MOPOE_LATENT_JSD
+
+
+def _mixture_args(method, mu_in, member_row_start, comp_row_start, w):
+    if method not in LATENT_METHODS:
+        raise MopoeHipError(f"latent_mixture: method must be one of {sorted(LATENT_METHODS)}, not {method!r}")
+    n = sum(t is not None for t in mu_in)
+    c = n + (method == "jsd")
+    if len(comp_row_start) != c + 1 or len(w) != c:
+        raise MopoeHipError(f"latent_mixture: {method} with {n} modalities takes {c} components")
+    flat = [v for part in member_row_start for v in (list(part) + [0] * 4)[:4]]
+    if len(flat) != 12:
+        raise MopoeHipError("latent_mixture: member_row_start holds the partitions over 1, 2 and 3 members")
+    return (LATENT_METHODS[method], c, (C.c_int32 * 12)(*flat), (C.c_int32 * (c + 1))(*comp_row_start),
+            (C.c_float * c)(*w))
+
+
+def latent_mixture_fwd(method, mu_in, lv_in, eps, member_row_start, comp_row_start, w, norm):
+    """method 'moe' or 'jsd'; mu_in/lv_in: 3-lists (PA, Lateral, text) of [B,D] or None; member_row_start: the row
+    partitions over 1, 2 and 3 subset members; comp_row_start [C+1] / w [C]: the joint's partition over the C components
+    and the joint divergence weights.
+    -> sub_mu, sub_lv [K,B,D], comp_mu, comp_lv [C,B,D], joint_mu, joint_lv, z, klds [K], individual_divs [C],
+       joint_div [1], pd_mu, pd_lv (jsd; None for moe)"""
+    present = [t for t in mu_in if t is not None]
+    _dev(*present, *[t for t in lv_in if t is not None], eps)
+    b, d = present[0].shape
+    m, c, mrs, crs, wa = _mixture_args(method, mu_in, member_row_start, comp_row_start, w)
+    k = (1 << len(present)) - 1
+    dev = present[0].device
+    sub_mu = torch.empty(k, b, d, dtype=torch.float32, device=dev)
+    sub_lv = torch.empty_like(sub_mu)
+    comp_mu = torch.empty(c, b, d, dtype=torch.float32, device=dev)
+    comp_lv = torch.empty_like(comp_mu)
+    jm, jl, z = (torch.empty(b, d, dtype=torch.float32, device=dev) for _ in range(3))
+    klds = torch.empty(k, dtype=torch.float32, device=dev)
+    indiv = torch.empty(c, dtype=torch.float32, device=dev)
+    jd = torch.empty(1, dtype=torch.float32, device=dev)
+    pd_mu, pd_lv = (torch.empty(b, d, dtype=torch.float32, device=dev) for _ in range(2)) if method == "jsd" \
+        else (None, None)
+    _check(lib().mopoe_latent_mixture_fwd(m, _ptr3(mu_in), _ptr3(lv_in), _p(eps), b, d, mrs, crs, wa, C.c_float(norm),
+                                          _p(sub_mu), _p(sub_lv), _p(comp_mu), _p(comp_lv), _p(jm), _p(jl), _p(z),
+                                          _p(klds), _p(indiv), _p(jd), _p(pd_mu), _p(pd_lv), _p(_ws(dev, 16)),
+                                          _stream()))
+    return sub_mu, sub_lv, comp_mu, comp_lv, jm, jl, z, klds, indiv, jd, pd_mu, pd_lv
+
+
+def latent_mixture_bwd(method, mu_in, lv_in, eps, member_row_start, comp_row_start, w, norm, g_sub_mu, g_sub_lv,
+                       g_comp_mu, g_comp_lv, g_jm, g_jl, g_z, g_klds, g_indiv, g_jd, g_pd_mu=None, g_pd_lv=None):
+    """-> (d_mu_in[3], d_lv_in[3]) with None for absent modalities; every g_* may be None."""
+    gs = (g_sub_mu, g_sub_lv, g_comp_mu, g_comp_lv, g_jm, g_jl, g_z, g_klds, g_indiv, g_jd, g_pd_mu, g_pd_lv)
+    present = [t for t in mu_in if t is not None]
+    _dev(*present, eps, *[t for t in gs if t is not None])
+    b, d = present[0].shape
+    m, _c, mrs, crs, wa = _mixture_args(method, mu_in, member_row_start, comp_row_start, w)
+    dmu = [None if t is None else torch.empty_like(t) for t in mu_in]
+    dlv = [None if t is None else torch.empty_like(t) for t in lv_in]
+    _check(lib().mopoe_latent_mixture_bwd(m, _ptr3(mu_in), _ptr3(lv_in), _p(eps), b, d, mrs, crs, wa, C.c_float(norm),
+                                          *[_p(t) for t in gs], _ptr3(dmu), _ptr3(dlv), _stream()))
     return dmu, dlv
 
 
