@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPOE_ABI_VERSION 20
+#define MOPOE_ABI_VERSION 21
 
 /* error codes */
 #define MOPOE_OK 0
@@ -293,6 +293,30 @@ int mopoe_latent_mixture_bwd(int32_t method, const float* const mu_in[3], const 
                              const float* g_klds, const float* g_individual_divs, const float* g_joint_div,
                              const float* g_pd_mu, const float* g_pd_lv, float* const d_mu_in[3],
                              float* const d_lv_in[3], void* stream);
+
+/* ---- style latents of the factorized representation --------------------------------------------------
+ * One kernel for the per-modality style draws of VAEtrimodalMimic.forward (mimic/networks/VAEtrimodalMimic.py:31-62 with
+ * utils.reparameterize, utils/utils.py:45-48), the decoders' torch.cat((z_style, z_content), dim=1)
+ * (ConvNetworksImgMimic.py:43-49, ConvNetworksTextMimic.py:43-54) and losses.calc_klds_style (evaluation/losses.py:34-42,
+ * kl_div.py:8-16), for all three modalities; it runs after mopoe_latent_fwd / mopoe_latent_mixture_fwd and reads their z.
+ *   smu/slv/eps_s[3]: per-modality style (mu, logvar) and N(0,1) noise [B, S[m]] in the order PA, Lateral, text; all three
+ *       NULL for an absent modality.  S[3]: HOST array of style dims (>= 1 for a present modality, any value).
+ *   z [B, D]: the content sample.  norm: flags.batch_size.
+ *   outputs: zcat[m] [B, S[m] + D] = [eps * exp(0.5 * logvar) + mu | z] (style columns first) for present m;
+ *       klds_style [3] = KL(N(mu_m, logvar_m) || N(0, I)) / norm (0 for an absent modality).
+ *       ws: double[4] workspace that must be zero on entry and is left zero. */
+int mopoe_latent_style_fwd(const float* const smu[3], const float* const slv[3], const float* const eps_s[3],
+                           const int32_t S[3], int32_t B, int32_t D, const float* z, float norm, float* const zcat[3],
+                           float* klds_style, double* ws, void* stream);
+
+/* backward: g_zcat[m] and g_klds_style [3] may be NULL (g_zcat itself too).  Overwrites, for present m,
+ *   d_smu[m] = g_zs + g_kl * mu / norm,  d_slv[m] = g_zs * eps * 0.5 * exp(0.5 * logvar) + g_kl * 0.5 * (exp(logvar) - 1) / norm
+ * (g_zs: the style columns of g_zcat[m]), and g_z [B, D] = the sum over present m of the content columns of g_zcat[m]
+ * (zero where no g_zcat is given): the z gradient that mopoe_latent_bwd / mopoe_latent_mixture_bwd then take. */
+int mopoe_latent_style_bwd(const float* const smu[3], const float* const slv[3], const float* const eps_s[3],
+                           const int32_t S[3], int32_t B, int32_t D, float norm, const float* const g_zcat[3],
+                           const float* g_klds_style, float* const d_smu[3], float* const d_slv[3], float* g_z,
+                           void* stream);
 
 /* ---- likelihoods -----------------------------------------------------------------------------------
  * Laplace(loc = x_hat, scale): out[0] = -sum log p(x | x_hat) / norm

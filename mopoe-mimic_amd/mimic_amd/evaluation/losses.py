@@ -31,9 +31,41 @@ def calc_klds(exp, result):
             for key, (mu, lv) in lat["subsets"].items()}
 
 
+def calc_klds_style(exp, result):
+    """KL(q_style_m || N(0,I)) / flags.batch_size per '<m>_style' key (losses.py:34-42).  The style kernel already produced
+    them (latents['_klds_style'], slots PA, Lateral, text): views, no recomputation."""
+    lat = result["latents"]
+    ks = lat.get("_klds_style")
+    out = {}
+    for key, (mu, lv) in lat["modalities"].items():
+        if not key.endswith("style"):
+            continue
+        if ks is not None:
+            out[key] = ks[("PA_style", "Lateral_style", "text_style").index(key)]
+        elif mu is not None:
+            out[key] = -0.5 * torch.sum(1 - lv.exp() - mu.pow(2) + lv) / float(exp.flags.batch_size)
+    return out
+
+
+def _style_weight_vec(exp, device):
+    """exp.style_weights (beta_m{1,2,3}_style) as a device vector in slot order, cached like calc_log_probs' rec weights"""
+    w = tuple(float(exp.style_weights[m]) for m in ("PA", "Lateral", "text"))
+    cache = getattr(exp, "_style_weight_vec", None)
+    if cache is None or cache[0] != w or cache[1].device != device:
+        cache = (w, torch.tensor(w, dtype=torch.float32, device=device))
+        exp._style_weight_vec = cache
+    return cache[1]
+
+
 def calc_joint_elbo_loss(exp, klds_style, group_divergence, beta_style, beta_content, weighted_log_prob, beta):
     if exp.flags.factorized_representation:
-        raise NotImplementedError("style latents are out of scope")
+        # beta * (beta_style * sum_m style_weight_m * kld_style_m + beta_content * group_divergence) (losses.py:45-51,80-89)
+        # from the style kernel's klds vector [3]: one dot product on the device, no host sync
+        ks = klds_style
+        if isinstance(ks, dict):
+            ks = torch.stack([ks[m + "_style"].reshape(()) for m in ("PA", "Lateral", "text")])
+        kld_style = (ks * _style_weight_vec(exp, ks.device)).sum()
+        return weighted_log_prob + float(beta) * (float(beta_style) * kld_style + float(beta_content) * group_divergence)
     # (reference losses.py:80-89: rec_weight 1.0, beta * (beta_style * 0 + beta_content * group_divergence); the python
     # coefficients are folded, one multiply + one add on the device)
     return weighted_log_prob + (float(beta) * float(beta_content)) * group_divergence

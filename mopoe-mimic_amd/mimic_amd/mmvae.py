@@ -121,6 +121,36 @@ class _LatentMixture(torch.autograd.Function):
         return (None, None, None, None, None, None, None, *grads)
 
 
+class _LatentStyle(torch.autograd.Function):
+    """style stage of the factorized representation, after the content latent node: z + the present modalities' style
+    (mu, logvar) + their noise -> the decoder inputs zcat_m = [z_style_m | z] (3, None for absent modalities) and
+    klds_style [3]."""
+
+    @staticmethod
+    def forward(ctx, present, eps_s, norm, z, *enc):
+        smu, slv, j = [None] * 3, [None] * 3, 0
+        for slot in range(3):
+            if present[slot]:
+                smu[slot], slv[slot] = enc[j].contiguous(), enc[j + 1].contiguous()
+                j += 2
+        z = z.contiguous()
+        zcat, klds = ops.latent_style_fwd(smu, slv, eps_s, z, norm)
+        ctx.args = (smu, slv, eps_s, z.shape[1], norm, present)
+        ctx.set_materialize_grads(False)
+        return (*zcat, klds)
+
+    @staticmethod
+    def backward(ctx, g0, g1, g2, g_klds):
+        smu, slv, eps_s, d, norm, present = ctx.args
+        c = lambda t: None if t is None else t.contiguous()
+        dmu, dlv, g_z = ops.latent_style_bwd(smu, slv, eps_s, d, norm, [c(g0), c(g1), c(g2)], c(g_klds))
+        grads = []
+        for slot in range(3):
+            if present[slot]:
+                grads += [dmu[slot], dlv[slot]]
+        return (None, None, None, g_z, *grads)
+
+
 class BaseMMVae(ABC, nn.Module):
     def __init__(self, flags, modalities, subsets):
         super().__init__()
@@ -129,6 +159,8 @@ class BaseMMVae(ABC, nn.Module):
         self.modalities = modalities
         self.subsets = subsets
         self.eps_source = None  # tests inject the reference's noise here: callable (B, D, device) -> tensor
+        # ... and the style noise of the factorized representation here: callable (m_key, B, S, device) -> tensor
+        self.style_eps_source = None
         self.set_fusion_functions()
 
     @abstractmethod
@@ -164,6 +196,11 @@ class BaseMMVae(ABC, nn.Module):
         if self.eps_source is not None:
             return self.eps_source(b, d, device).contiguous()
         return torch.randn(b, d, device=device)
+
+    def _draw_style_eps(self, m_key, b, s, device):
+        if self.style_eps_source is not None:
+            return self.style_eps_source(m_key, b, s, device).contiguous()
+        return torch.randn(b, s, device=device)
 
     def inference(self, input_batch, num_samples=None) -> Mapping[str, any]:
         """BaseMMVae.inference (:139-196): accepts partial modality dicts."""
@@ -244,8 +281,19 @@ class BaseMMVae(ABC, nn.Module):
 class VAEtrimodalMimic(BaseMMVae, nn.Module):
     def __init__(self, flags, modalities, subsets):
         super().__init__(flags, modalities, subsets)
-        if getattr(flags, "factorized_representation", False):
-            raise NotImplementedError("factorized_representation is out of scope (SURVEY §2.1-4)")
+        dims = {"style_pa_dim": flags.style_pa_dim, "style_lat_dim": flags.style_lat_dim,
+                "style_text_dim": flags.style_text_dim}
+        self.factorized = bool(getattr(flags, "factorized_representation", False))
+        # the two combinations the reference cannot run: encode() stores no '<m>_style' pair (forward: KeyError), or the
+        # decoders' feature_generator expects [z_style | z] and gets z (shape mismatch)
+        if self.factorized and any(v <= 0 for v in dims.values()):
+            bad = ", ".join(k for k, v in dims.items() if v <= 0)
+            raise ValueError(f"factorized_representation needs style_pa_dim, style_lat_dim and style_text_dim > 0; "
+                             f"{bad} = 0")
+        if not self.factorized and any(v > 0 for v in dims.values()):
+            bad = ", ".join(f"{k}={v}" for k, v in dims.items() if v > 0)
+            raise ValueError(f"{bad} without factorized_representation: the style latents are used only with "
+                             "factorized_representation=True")
         dev = flags.device
         self.encoder_pa = modalities["PA"].encoder.to(dev)
         self.encoder_lat = modalities["Lateral"].encoder.to(dev)
@@ -271,8 +319,11 @@ class VAEtrimodalMimic(BaseMMVae, nn.Module):
                    "individual_divs": latents.get("_individual_divs", latents["_klds"]),
                    "dyn_prior": latents.get("_dyn_prior")}
         z = latents["_z"]
+        dec_in = {m_key: (None, z) for m_key in MOD_SLOT}
+        if self.factorized:
+            dec_in = self._style_stage(latents, input_batch, z)
         # the decoders are independent: one grouped autograd node, each network on its modality's stream (nets.run_group)
-        items = [(m_key, net, (None, z))
+        items = [(m_key, net, dec_in[m_key])
                  for m_key, net in (("Lateral", self.decoder_lat), ("PA", self.decoder_pa), ("text", self.decoder_text))
                  if m_key in self.modalities and input_batch[m_key] is not None]
         dec = dict(zip([m for m, _, _ in items], run_group(items)))
@@ -289,21 +340,48 @@ class VAEtrimodalMimic(BaseMMVae, nn.Module):
         results["rec"] = rec
         return results
 
+    def _style_stage(self, latents, input_batch, z):
+        """style draws (after the content noise, in the order PA, Lateral, text: VAEtrimodalMimic.py:31-62) and the
+        decoder inputs [z_style_m | z], in one node (_LatentStyle); latents['_klds_style'] [3] is its KL by-product"""
+        from .nets import ZCAT
+        mods = latents["modalities"]
+        present = tuple(name in input_batch and mods.get(name + "_style", [None])[0] is not None for name in MOD_SLOT)
+        eps_s, enc = [None] * 3, []
+        for name, slot in MOD_SLOT.items():
+            if present[slot]:
+                mu, lv = mods[name + "_style"]
+                eps_s[slot] = self._draw_style_eps(name, mu.shape[0], mu.shape[1], mu.device)
+                enc += [mu, lv]
+        outs = _LatentStyle.apply(present, eps_s, float(self.flags.batch_size), z, *enc)
+        latents["_klds_style"] = outs[3]
+        return {name: (ZCAT, outs[slot]) for name, slot in MOD_SLOT.items()}
+
     def encode(self, input_batch):
+        """{'PA', 'PA_style', 'Lateral', 'Lateral_style', 'text', 'text_style'} in the reference's key order
+        (VAEtrimodalMimic.py:64-93); the '<m>_style' pairs exist when the encoders have style heads, and are [None, None]
+        for an absent modality"""
+        items = [(name, enc, (input_batch[name],))
+                 for name, enc in (("PA", self.encoder_pa), ("Lateral", self.encoder_lat), ("text", self.encoder_text))
+                 if name in input_batch.keys()]
+        outs = {name: list(out) for (name, _, _), out in zip(items, run_group(items))}
         latents = {}
-        items = []
-        for name, enc in (("PA", self.encoder_pa), ("Lateral", self.encoder_lat), ("text", self.encoder_text)):
-            if name in input_batch.keys():
-                items.append((name, enc, (input_batch[name],)))
-            else:
+        for name in MOD_SLOT:
+            if name not in outs:
                 latents[name + "_style"] = [None, None]
                 latents[name] = [None, None]
-        for (name, _, _), out in zip(items, run_group(items)):
-            latents[name] = list(out)[:2]
+                continue
+            latents[name] = outs[name][:2]
+            if len(outs[name]) == 4:
+                latents[name + "_style"] = outs[name][2:]
         return latents
 
     def get_random_styles(self, num_samples):
-        return {"PA": None, "Lateral": None, "text": None}
+        """N(0, I) styles for generation (VAEtrimodalMimic.py:95-107; tests inject them through style_eps_source)"""
+        if not self.factorized:
+            return {"PA": None, "Lateral": None, "text": None}
+        f, dev = self.flags, self.flags.device
+        return {m: self._draw_style_eps(m, num_samples, s, dev)
+                for m, s in (("PA", f.style_pa_dim), ("Lateral", f.style_lat_dim), ("text", f.style_text_dim))}
 
     def get_random_style_dists(self, num_samples):
         dev, f = self.flags.device, self.flags

@@ -274,41 +274,68 @@ class _FeatureExtractorImg(nn.Module):
 
 
 class _Compressor(nn.Module):
-    """LinearFeatureCompressor (FeatureCompressor.py:4-28) without the style branch."""
+    """LinearFeatureCompressor (FeatureCompressor.py:4-28); style_dim > 0 adds the style heads of the factorized
+    representation (same names and layouts as the reference's nn.Linear)."""
 
     def __init__(self, cin, style_dim, cout):
         super().__init__()
         if style_dim:
-            raise NotImplementedError("factorized_representation / style latents are out of scope (SURVEY §2.1-4)")
-        self.style_mu = None
-        self.style_logvar = None
+            self.style_mu = PackedConv(cin, style_dim, (), "linear", True)
+            self.style_logvar = PackedConv(cin, style_dim, (), "linear", True)
+        else:
+            self.style_mu = None
+            self.style_logvar = None
         self.content_mu = PackedConv(cin, cout, (), "linear", True)
         self.content_logvar = PackedConv(cin, cout, (), "linear", True)
 
+    def heads(self):
+        """(name, module) of the heads in output order: content (mu, logvar), then style (mu, logvar) when present"""
+        out = [("content_mu", self.content_mu), ("content_logvar", self.content_logvar)]
+        if self.style_mu is not None:
+            out += [("style_mu", self.style_mu), ("style_logvar", self.style_logvar)]
+        return out
+
 
 def _compress_fwd(comp: _Compressor, feat, batch, w=lambda m: m.weight):
-    """(mu, logvar) are fp32 in either family: they feed the fp32 latent kernel"""
-    g = _lin_geom(comp.content_mu.cin, comp.content_mu.cout).with_batch(batch)
-    mu = ops.conv_fwd(feat, w(comp.content_mu), g, bias=comp.content_mu.bias, out_dtype=torch.float32)
-    lv = ops.conv_fwd(feat, w(comp.content_logvar), g, bias=comp.content_logvar.bias, out_dtype=torch.float32)
-    return mu.view(batch, -1), lv.view(batch, -1), g
+    """(mu, logvar[, style_mu, style_logvar]) are fp32 in either family: they feed the fp32 latent kernels.
+    -> (outputs, per-head geometries)"""
+    outs, geoms = [], []
+    for _name, mod in comp.heads():
+        g = _lin_geom(mod.cin, mod.cout).with_batch(batch)
+        outs.append(ops.conv_fwd(feat, w(mod), g, bias=mod.bias, out_dtype=torch.float32).view(batch, -1))
+        geoms.append(g)
+    return tuple(outs), geoms
 
 
-def _compress_bwd(comp: _Compressor, feat, g, gmu, glv, grads, prefix, w=lambda m: m.weight, arena=None):
+def _compress_bwd(comp: _Compressor, feat, geoms, gouts, grads, prefix, w=lambda m: m.weight, arena=None):
+    """gouts: gradients of the heads' outputs in heads() order (None where none arrived); the data gradients of all heads
+    are summed into one dfeat"""
     batch = feat.shape[0]
     dfeat = None
     take = (lambda shape: arena.take_misc(shape)) if arena is not None else (lambda shape: None)
-    for name, mod, gg in (("content_mu", comp.content_mu, gmu), ("content_logvar", comp.content_logvar, glv)):
+    for (name, mod), g, gg in zip(comp.heads(), geoms, gouts):
         if gg is None:
             continue
         gg4 = gg.reshape(batch, 1, 1, -1)
         grads[f"{prefix}.{name}.bias"] = ops.colsum(gg4, out=take((gg4.shape[-1],)))
+        gg32 = gg4
         if feat.dtype != gg4.dtype:      # bf16 family: the gradient enters the GEMMs as a bf16 operand
             gg4 = gg4.to(feat.dtype)
         grads[f"{prefix}.{name}.weight"] = ops.conv_wgrad(feat, gg4, g, out=take((g.taps, g.Cin, g.Cout)))
-        d = ops.conv_dgrad(gg4, w(mod), g, out_dtype=torch.float32)   # the two halves are summed in fp32, stored once
+        if gg4.dtype != gg32.dtype and mod.cout % 32:
+            # bf16 family, a head narrower than the bf16 GEMMs' K granularity (a style dim): its data gradient is formed in
+            # fp32 on the master weight
+            d = ops.conv_dgrad(gg32, mod.weight, g)
+        else:
+            d = ops.conv_dgrad(gg4, w(mod), g, out_dtype=torch.float32)   # the heads' data gradients are summed in fp32, stored once
         dfeat = d if dfeat is None else dfeat.add_(d)
     return dfeat if dfeat is None or dfeat.dtype == feat.dtype else dfeat.to(feat.dtype)
+
+
+def _enc_out_names(comp: _Compressor):
+    """an encoder returns (mu, logvar) of the content, then (mu, logvar) of the style when it has style heads
+    (ConvNetworksImgMimic.py:30-33, ConvNetworksTextMimic.py:31-33)"""
+    return ("mu", "logvar", "style_mu", "style_logvar") if comp.style_mu is not None else ("mu", "logvar")
 
 
 class EncoderImg(_HipNet):
@@ -332,14 +359,19 @@ class EncoderImg(_HipNet):
             h = ho
         assert h == 1
         self._init_dtype(flags, fp32_mods=[self.feature_extractor.conv1])
+        if self._bf16() and style_dim % 8:
+            raise NotImplementedError(f"the bf16 family needs style dims that are multiples of 8 (the bf16 GEMMs' output "
+                                      f"granularity), not {style_dim}")
 
-    _out_names = ("mu", "logvar")
+    @property
+    def _out_names(self):
+        return _enc_out_names(self.feature_compressor)
 
     def _group_inputs(self, x_img):
         return (x_img,)
 
     def _finish(self, outs):
-        return outs[0], outs[1]
+        return tuple(outs)
 
     def forward(self, x_img):
         return self._finish(self._call(*self._group_inputs(x_img)))
@@ -357,15 +389,15 @@ class EncoderImg(_HipNet):
         h0 = ops.conv_fwd(x, fe.conv1.weight, gs, out_stats=st0, out_dtype=self.act_dtype)
         feat, saved, running = trunk_forward(self.blocks, h0, st0, self.training, self._dropout_on(),
                                              self.mask_source, arena, b, self._w)
-        mu, lv, gl = _compress_fwd(self.feature_compressor, feat, b, self._w)
+        outs, gl = _compress_fwd(self.feature_compressor, feat, b, self._w)
         if self.training:
             apply_running_updates(running)
-        return (mu, lv), dict(x=x, feat=feat, trunk=saved, gs=gs, gl=gl, arena=arena)
+        return outs, dict(x=x, feat=feat, trunk=saved, gs=gs, gl=gl, arena=arena)
 
-    def _run_backward(self, sv, in_needs_grad, gmu, glv):
+    def _run_backward(self, sv, in_needs_grad, *gouts):
         grads: Dict[str, torch.Tensor] = {}
         ar = BackwardArena(self.blocks, sv["feat"].device, extra=self._misc_numel())
-        dfeat = _compress_bwd(self.feature_compressor, sv["feat"], sv["gl"], gmu, glv, grads, "feature_compressor", self._w, ar)
+        dfeat = _compress_bwd(self.feature_compressor, sv["feat"], sv["gl"], gouts, grads, "feature_compressor", self._w, ar)
         g0, arena = trunk_backward(self.blocks, sv["trunk"], dfeat, grads, self._w, ar)
         gs = sv["gs"]
         grads["feature_extractor.conv1.weight"] = ops.conv_wgrad(sv["x"], g0, gs, out=ar.take_misc((gs.taps, gs.Cin, gs.Cout)))
@@ -381,6 +413,78 @@ class EncoderImg(_HipNet):
 # =================================================================================================
 # image decoder
 # =================================================================================================
+class ZCat:
+    """z_style argument of a decoder meaning "z_content is already the decoder input [z_style | z]" (the model's own path:
+    ops.latent_style_fwd writes it)"""
+
+
+ZCAT = ZCat()
+
+
+def _fg_init(dec, flags):
+    """bf16 family: the bf16 GEMMs take K in multiples of 32, and a style dim makes the feature generator's K = S + class_dim
+    ragged; its input and a bf16 copy of its weight are then zero-padded along K (dec._fg_kpad, 0 when not needed)"""
+    k = dec.feature_generator.cin
+    kpad = -(-k // 32) * 32 if compute_dtype(flags) == torch.bfloat16 and k % 32 else 0
+    object.__setattr__(dec, "_fg_kpad", kpad)
+    object.__setattr__(dec, "_fg_pad_w", None)
+    return [dec.feature_generator] if kpad else []    # (kept out of the bf16 shadow: the padded copy stands in for it)
+
+
+def _fg_weight(dec):
+    if not dec._fg_kpad:
+        return dec._w(dec.feature_generator)
+    w = dec.feature_generator.weight
+    hp = dec._fg_pad_w
+    if hp is None or hp[0].device != w.device:
+        hp = [torch.zeros(1, dec._fg_kpad, w.shape[2], dtype=dec.act_dtype, device=w.device), None]
+        object.__setattr__(dec, "_fg_pad_w", hp)
+    vers = (param_epoch(), w._version)
+    if dec.training or vers != hp[1]:
+        with torch.no_grad():
+            hp[0][:, :w.shape[1]].copy_(w)
+        hp[1] = vers
+    return hp[0]
+
+
+def _fg_forward(dec, z, b, arena):
+    """the feature generator (nn.Linear(S + class_dim, 5 DIM)) on the decoder input -> (h0, its stats, z4, geometry)"""
+    z4 = z.contiguous().view(b, 1, 1, -1).to(dec.act_dtype)
+    if dec._fg_kpad:
+        z4 = torch.nn.functional.pad(z4, (0, dec._fg_kpad - z4.shape[-1]))
+    gl = _lin_geom(z4.shape[-1], dec.feature_generator.cout).with_batch(b)
+    st0 = arena.take(gl.Cout)
+    h0 = ops.conv_fwd(z4, _fg_weight(dec), gl, bias=dec.feature_generator.bias, out_stats=st0)
+    return h0, st0, z4, gl
+
+
+def _fg_backward(dec, sv, g0, grads, ar, need_gz):
+    """the feature generator's gradients; -> the gradient of the decoder input (fp32) or None"""
+    gl, b = sv["gl"], g0.shape[0]
+    if dec._fg_kpad:
+        k = dec.feature_generator.cin
+        grads["feature_generator.weight"] = ops.conv_wgrad(sv["z4"], g0, gl)[:, :k].contiguous()
+    else:
+        grads["feature_generator.weight"] = ops.conv_wgrad(sv["z4"], g0, gl, out=ar.take_misc((gl.taps, gl.Cin, gl.Cout)))
+    grads["feature_generator.bias"] = ops.colsum(g0, out=ar.take_misc((g0.shape[-1],)))
+    if not need_gz:
+        return None
+    gz = ops.conv_dgrad(g0, _fg_weight(dec), gl, out_dtype=torch.float32).view(b, -1)
+    return gz[:, :dec.feature_generator.cin] if dec._fg_kpad else gz
+
+
+def _decoder_input(dec, z_style, z_content):
+    """the feature generator's input: z (no style), the kernel-written [z_style | z] (z_style is ZCAT), or the public
+    forward's torch.cat((z_style, z_content), dim=1) (ConvNetworksImgMimic.py:43-49, ConvNetworksTextMimic.py:43-54)"""
+    if isinstance(z_style, ZCat):
+        return z_content
+    if not dec.style_dim:
+        return z_content
+    if z_style is None:
+        raise ValueError(f"{type(dec).__name__} has style_dim {dec.style_dim} (factorized_representation): "
+                         "forward(z_style, z_content) needs z_style")
+    return torch.cat((z_style, z_content), dim=1)
+
 class _DataGeneratorImg(nn.Module):
     def __init__(self, flags):
         super().__init__()
@@ -401,11 +505,10 @@ class DecoderImg(_HipNet):
 
     def __init__(self, flags, style_dim):
         super().__init__()
-        if style_dim:
-            raise NotImplementedError("style latents are out of scope (SURVEY §2.1-4)")
         self.flags = flags
+        self.style_dim = style_dim
         d = flags.DIM_img
-        self.feature_generator = PackedConv(flags.class_dim, 5 * d, (), "linear", True)
+        self.feature_generator = PackedConv(style_dim + flags.class_dim, 5 * d, (), "linear", True)
         self.img_generator = _DataGeneratorImg(flags)
         self.blocks: List[BlockSpec] = []
         h = 1
@@ -421,7 +524,7 @@ class DecoderImg(_HipNet):
         self.head_geom = Geom(1, h, h, 2 * h, 2 * h, d, flags.image_channels, 3, 3, 2, 2, 1, 1, True)
         assert 2 * h == flags.img_size
         self._scale_cache = {}
-        self._init_dtype(flags, fp32_mods=[self.head])
+        self._init_dtype(flags, fp32_mods=[self.head] + _fg_init(self, flags))
 
     @property
     def head(self):
@@ -438,7 +541,7 @@ class DecoderImg(_HipNet):
     _out_names = ("img",)
 
     def _group_inputs(self, z_style, z_content):
-        return (z_content,)
+        return (_decoder_input(self, z_style, z_content),)
 
     def _finish(self, outs):
         return outs[0], self._scale(outs[0].device)
@@ -449,11 +552,8 @@ class DecoderImg(_HipNet):
     def _run_forward(self, z):
         self._begin_forward()
         b = z.shape[0]
-        z4 = z.contiguous().view(b, 1, 1, -1).to(self.act_dtype)
         arena = self._arena(self.blocks, z.device)
-        gl = _lin_geom(self.feature_generator.cin, self.feature_generator.cout).with_batch(b)
-        st0 = arena.take(gl.Cout)
-        h0 = ops.conv_fwd(z4, self._w(self.feature_generator), gl, bias=self.feature_generator.bias, out_stats=st0)
+        h0, st0, z4, gl = _fg_forward(self, z, b, arena)
         ht, saved, running = trunk_forward(self.blocks, h0, st0, self.training, self._dropout_on(),
                                            self.mask_source, arena, b, self._w)
         gh = self.head_geom.with_batch(b)
@@ -476,10 +576,7 @@ class DecoderImg(_HipNet):
         grads[f"img_generator.generator.{k}.bias"] = ops.colsum(g4, out=ar.take_misc((g4.shape[-1],)))
         dht = ops.conv_dgrad(g4, self.head.weight, sv["gh"], out_dtype=self.act_dtype)
         g0, arena = trunk_backward(self.blocks, sv["trunk"], dht, grads, self._w, ar)
-        grads["feature_generator.weight"] = ops.conv_wgrad(sv["z4"], g0, gl, out=ar.take_misc((gl.taps, gl.Cin, gl.Cout)))
-        grads["feature_generator.bias"] = ops.colsum(g0, out=ar.take_misc((g0.shape[-1],)))
-        gz = ops.conv_dgrad(g0, self._w(self.feature_generator), sv["gl"], out_dtype=torch.float32).view(b, -1) \
-            if in_needs_grad[0] else None
+        gz = _fg_backward(self, sv, g0, grads, ar, in_needs_grad[0])
         return [gz], grads, arena
 
 
@@ -540,14 +637,19 @@ class EncoderText(_HipNet):
             w = wo
         assert w == 1, "text encoder must reduce the sequence to length 1"
         self._init_dtype(flags)
+        if self._bf16() and style_dim % 8:
+            raise NotImplementedError(f"the bf16 family needs style dims that are multiples of 8 (the bf16 GEMMs' output "
+                                      f"granularity), not {style_dim}")
 
-    _out_names = ("mu", "logvar")
+    @property
+    def _out_names(self):
+        return _enc_out_names(self.feature_compressor)
 
     def _group_inputs(self, x_text):
         return (x_text,)
 
     def _finish(self, outs):
-        return outs[0], outs[1]
+        return tuple(outs)
 
     def forward(self, x_text):
         return self._finish(self._call(*self._group_inputs(x_text)))
@@ -567,16 +669,16 @@ class EncoderText(_HipNet):
         h0 = ops.conv_fwd(emb, self._w(fe.conv1), gs, bias=fe.conv1.bias, out_stats=st0)
         feat, saved, running = trunk_forward(self.blocks, h0, st0, self.training, self._dropout_on(),
                                              self.mask_source, arena, b, self._w)
-        mu, lv, gl = _compress_fwd(self.feature_compressor, feat, b, self._w)
+        outs, gl = _compress_fwd(self.feature_compressor, feat, b, self._w)
         if self.training:
             apply_running_updates(running)
-        return (mu, lv), dict(ids=ids, emb=emb, feat=feat, trunk=saved, gs=gs, gl=gl, arena=arena)
+        return outs, dict(ids=ids, emb=emb, feat=feat, trunk=saved, gs=gs, gl=gl, arena=arena)
 
-    def _run_backward(self, sv, in_needs_grad, gmu, glv):
+    def _run_backward(self, sv, in_needs_grad, *gouts):
         grads: Dict[str, torch.Tensor] = {}
         fe = self.feature_extractor
         ar = BackwardArena(self.blocks, sv["feat"].device, extra=self._misc_numel())
-        dfeat = _compress_bwd(self.feature_compressor, sv["feat"], sv["gl"], gmu, glv, grads, "feature_compressor", self._w, ar)
+        dfeat = _compress_bwd(self.feature_compressor, sv["feat"], sv["gl"], gouts, grads, "feature_compressor", self._w, ar)
         g0, arena = trunk_backward(self.blocks, sv["trunk"], dfeat, grads, self._w, ar)
         gs = sv["gs"]
         grads["feature_extractor.conv1.weight"] = ops.conv_wgrad(sv["emb"], g0, gs, out=ar.take_misc((gs.taps, gs.Cin, gs.Cout)))
@@ -622,16 +724,15 @@ class _DataGeneratorText(nn.Module):
 class DecoderText(_HipNet):
     def __init__(self, flags, style_dim):
         super().__init__()
-        if style_dim:
-            raise NotImplementedError("style latents are out of scope (SURVEY §2.1-4)")
         if flags.text_encoding not in ("word", "char"):
             raise ValueError(f"text_encoding must be 'word' or 'char', not {flags.text_encoding!r}")
         self.flags = flags
+        self.style_dim = style_dim
         self.char = flags.text_encoding == "char"
         if self.char and compute_dtype(flags) == torch.bfloat16:
             raise NotImplementedError("the char text networks (71 output features) have no bf16 path")
         d = flags.DIM_text
-        self.feature_generator = PackedConv(flags.class_dim, 5 * d, (), "linear", True)
+        self.feature_generator = PackedConv(style_dim + flags.class_dim, 5 * d, (), "linear", True)
         self.text_generator = _DataGeneratorText(flags)
         self.blocks: List[BlockSpec] = []
         w = 1
@@ -652,7 +753,7 @@ class DecoderText(_HipNet):
             assert 2 * w == flags.len_sequence
             self.vocab = self.vpad = nf
             self.head_geom_pad = self.head_geom
-            self._init_dtype(flags)
+            self._init_dtype(flags, fp32_mods=_fg_init(self, flags))
             object.__setattr__(self, "_head_pad", None)
             return
         assert w == flags.len_sequence
@@ -663,7 +764,7 @@ class DecoderText(_HipNet):
         # The logits and log-probabilities are fp32 in either family.
         self.vocab, self.vpad = flags.vocab_size, -(-flags.vocab_size // 32) * 32
         self.head_geom_pad = Geom(1, 1, w, 1, w, d, self.vpad, 1, 1, 1, 1, 0, 0, False)
-        self._init_dtype(flags, fp32_mods=[self.head])
+        self._init_dtype(flags, fp32_mods=[self.head] + _fg_init(self, flags))
         object.__setattr__(self, "_head_pad", None)
 
     def _padded_head(self):
@@ -702,11 +803,12 @@ class DecoderText(_HipNet):
 
     def _group_inputs(self, z_style, z_content):
         object.__setattr__(self, "_lazy_call", bool(self.lazy_head and not self.char))
-        return (z_content,)
+        return (_decoder_input(self, z_style, z_content),)
 
     def forward(self, z_style, z_content):
+        zin = _decoder_input(self, z_style, z_content)
         object.__setattr__(self, "_lazy_call", False)
-        return self._finish(self._call(z_content))
+        return self._finish(self._call(zin))
 
     def _finish(self, outs):
         hc = getattr(self, "_head_ctx_latest", None)
@@ -726,11 +828,8 @@ class DecoderText(_HipNet):
     def _run_forward(self, z):
         self._begin_forward()
         b = z.shape[0]
-        z4 = z.contiguous().view(b, 1, 1, -1).to(self.act_dtype)
         arena = self._arena(self.blocks, z.device)
-        gl = _lin_geom(self.feature_generator.cin, self.feature_generator.cout).with_batch(b)
-        st0 = arena.take(gl.Cout)
-        h0 = ops.conv_fwd(z4, self._w(self.feature_generator), gl, bias=self.feature_generator.bias, out_stats=st0)
+        h0, st0, z4, gl = _fg_forward(self, z, b, arena)
         ht, saved, running = trunk_forward(self.blocks, h0, st0, self.training, self._dropout_on(),
                                            self.mask_source, arena, b, self._w)
         gh = self.head_geom_pad.with_batch(b)
@@ -823,8 +922,5 @@ class DecoderText(_HipNet):
             grads[f"text_generator.generator.{k}.bias"] = ops.colsum(glogits)[:self.vocab]
             dht = ops.conv_dgrad(glogits, w_pad, gh)
         g0, arena = trunk_backward(self.blocks, sv["trunk"], dht, grads, self._w, ar)
-        grads["feature_generator.weight"] = ops.conv_wgrad(sv["z4"], g0, gl, out=ar.take_misc((gl.taps, gl.Cin, gl.Cout)))
-        grads["feature_generator.bias"] = ops.colsum(g0, out=ar.take_misc((g0.shape[-1],)))
-        gz = ops.conv_dgrad(g0, self._w(self.feature_generator), sv["gl"], out_dtype=torch.float32).view(b, -1) \
-            if in_needs_grad[0] else None
+        gz = _fg_backward(self, sv, g0, grads, ar, in_needs_grad[0])
         return [gz], grads, arena

@@ -20,7 +20,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOPOE_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libmopoe_hip.so")  # env override: A/B builds
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 RES_A, RES_B = 2.0, 0.3
 BN_EPS = 1e-5
@@ -1038,6 +1038,55 @@ def latent_mixture_bwd(method, mu_in, lv_in, eps, member_row_start, comp_row_sta
     _check(lib().mopoe_latent_mixture_bwd(m, _ptr3(mu_in), _ptr3(lv_in), _p(eps), b, d, mrs, crs, wa, C.c_float(norm),
                                           *[_p(t) for t in gs], _ptr3(dmu), _ptr3(dlv), _stream()))
     return dmu, dlv
+
+
+def _style_args(smu, slv, eps_s):
+    present = [m for m in range(3) if smu[m] is not None]
+    if not present:
+        raise MopoeHipError("latent_style: no modality present")
+    for m in range(3):
+        if (smu[m] is None) != (slv[m] is None) or (smu[m] is None) != (eps_s[m] is None):
+            raise MopoeHipError(f"latent_style: slot {m}: mu / logvar / eps presence mismatch")
+    b = smu[present[0]].shape[0]
+    s = [0 if smu[m] is None else smu[m].shape[1] for m in range(3)]
+    for m in present:
+        if smu[m].dim() != 2 or smu[m].shape[0] != b or slv[m].shape != smu[m].shape or eps_s[m].shape != smu[m].shape:
+            raise MopoeHipError(f"latent_style: slot {m}: mu, logvar and eps must all be [B, S]")
+    return present, b, s, (C.c_int32 * 3)(*s)
+
+
+def latent_style_fwd(smu, slv, eps_s, z, norm):
+    """style stage after the content latent kernel.  smu/slv/eps_s: 3-lists (PA, Lateral, text) of [B,S_m] or None;
+    z [B,D] the content sample.
+    -> zcat (3-list of [B, S_m + D] = [z_style_m | z], None for absent modalities), klds_style [3]"""
+    present, b, s, sa = _style_args(smu, slv, eps_s)
+    _dev(*[t for ts in (smu, slv, eps_s) for t in ts if t is not None], z)
+    if z.dim() != 2 or z.shape[0] != b:
+        raise MopoeHipError("latent_style_fwd: z must be [B, D]")
+    d = z.shape[1]
+    zcat = [None if smu[m] is None else torch.empty(b, s[m] + d, dtype=torch.float32, device=z.device) for m in range(3)]
+    klds = torch.empty(3, dtype=torch.float32, device=z.device)
+    _check(lib().mopoe_latent_style_fwd(_ptr3(smu), _ptr3(slv), _ptr3(eps_s), sa, b, d, _p(z), C.c_float(norm),
+                                        _ptr3(zcat), _p(klds), _p(_ws(z.device, 4)), _stream()))
+    return zcat, klds
+
+
+def latent_style_bwd(smu, slv, eps_s, d, norm, g_zcat, g_klds):
+    """g_zcat: 3-list of [B, S_m + D] or None (or None); g_klds [3] or None.
+    -> (d_smu[3], d_slv[3]) with None for absent modalities, g_z [B, D]"""
+    present, b, s, sa = _style_args(smu, slv, eps_s)
+    g_zcat = list(g_zcat) if g_zcat is not None else [None] * 3
+    for m in range(3):
+        if g_zcat[m] is not None and (smu[m] is None or tuple(g_zcat[m].shape) != (b, s[m] + d)):
+            raise MopoeHipError(f"latent_style_bwd: slot {m}: g_zcat must be [B, S + D] of a present modality")
+    _dev(*[t for ts in (smu, slv, eps_s, g_zcat) for t in ts if t is not None], g_klds)
+    dev = smu[present[0]].device
+    dmu = [None if t is None else torch.empty_like(t) for t in smu]
+    dlv = [None if t is None else torch.empty_like(t) for t in slv]
+    g_z = torch.empty(b, d, dtype=torch.float32, device=dev)
+    _check(lib().mopoe_latent_style_bwd(_ptr3(smu), _ptr3(slv), _ptr3(eps_s), sa, b, d, C.c_float(norm), _ptr3(g_zcat),
+                                        _p(g_klds), _ptr3(dmu), _ptr3(dlv), _p(g_z), _stream()))
+    return dmu, dlv, g_z
 
 
 # ----------------------------------------------------------------------------------------------

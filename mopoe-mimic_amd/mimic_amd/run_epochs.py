@@ -21,7 +21,7 @@ from contextlib import contextmanager
 import numpy as np
 import torch
 
-from .evaluation.losses import calc_joint_elbo_loss, calc_klds, calc_log_probs
+from .evaluation.losses import calc_joint_elbo_loss, calc_klds, calc_klds_style, calc_log_probs
 from .layout import note_params_changed
 from .parallel import GradAllReducer
 from .utils.exceptions import CudaOutOfMemory, NaNInLatent
@@ -59,6 +59,12 @@ def basic_routine_epoch(exp, batch) -> typing.Mapping[str, any]:
         log_probs, weighted_log_prob = calc_log_probs(exp, results, batch)
     group_divergence = results["joint_divergence"]
     klds = calc_klds(exp, results)
+    if flags.factorized_representation:
+        klds_style = calc_klds_style(exp, results)
+        total_loss = calc_joint_elbo_loss(exp, results["latents"]["_klds_style"], group_divergence, flags.beta_style,
+                                          flags.beta_content, weighted_log_prob, flags.beta)
+        return {"results": results, "log_probs": log_probs, "total_loss": total_loss, "klds": klds,
+                "klds_style": klds_style}
     total_loss = calc_joint_elbo_loss(exp, None, group_divergence, flags.beta_style, flags.beta_content,
                                       weighted_log_prob, flags.beta)
     return {"results": results, "log_probs": log_probs, "total_loss": total_loss, "klds": klds}
@@ -87,6 +93,9 @@ class ScalarPack:
         for k, v in routine["klds"].items():
             names.append("klds/" + k)
             vals.append(v.detach().reshape(1))
+        for k, v in routine.get("klds_style", {}).items():
+            names.append("klds_style/" + k)
+            vals.append(v.detach().reshape(1))
         for k, v in routine["log_probs"].items():
             names.append("log_probs/" + k)
             vals.append(v.detach().reshape(1))
@@ -96,8 +105,10 @@ class ScalarPack:
                 continue
             names += [f"latents/{k}/mu", f"latents/{k}/logvar"]
             lat += [mu.detach(), lv.detach()]
-        if lat:   # (one stacked reduction instead of one mean per tensor)
+        if lat and all(t.shape == lat[0].shape for t in lat):   # (one stacked reduction instead of one mean per tensor)
             vals.append(torch.stack(lat).mean(dim=(1, 2)))
+        elif lat:   # (style latents of other widths: one mean per tensor)
+            vals.append(torch.stack([t.mean() for t in lat]))
         packed = torch.cat(vals)
         self.names = names
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
