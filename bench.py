@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- MoPoE joint-ELBO train step on MI355X (BASELINE.json metric: samples/sec).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2d128|c1|c3|c5] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2d128|c1|c3|c5] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-roofline]]
     N > 1:  either  python bench.py --gpus N ...   (no WORLD_SIZE in the environment: bench.py starts N fresh rank
                     processes itself, before anything in this process has touched a GPU -- the reference's launcher does
                     the same with mp.spawn, mimic/main_mimic.py:44-48,65-69)
@@ -19,12 +20,16 @@ DIM_img 64, DIM_text 128, vocab 3517, batch 64 per GPU, fp32, train mode (BatchN
 dropout on).  Weak scaling: 64 samples per GPU.
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline      the dominant kernel (fp32-MFMA implicit-GEMM) timed with HIP events on its launch stream
-                in a second pass of the same steps (so the events do not perturb `value`)
   ms_per_step   wall time of one timed step (the K timed steps between two device synchronisations, divided by K)
+A plain run does only what that line's headline needs: set-up, the W warm-up and K timed steps, --dump-outputs, the line.
+--full adds the measurements that take runs of their own (after the timed steps and the dump, so `value`, `ms_per_step`
+and the dumped arrays are the same either way); without --full their fields are null:
+  host_ms_per_step_call_idle_queue  (in `config`) host cost of one step call with an idle queue (3 more steps)
+  roofline      the dominant kernel (fp32-MFMA implicit-GEMM) timed with HIP events on its launch stream
+                in a second pass of the same steps (so the events do not perturb `value`); --no-roofline skips it
   cpu_baseline  the CPU oracle (oracle/mopoe_ref.py, a port) timed on this host's cores on a bounded
                 sample (3 warm-up + 10 timed steps of the default workload on 16 threads, ~45 s of CPU work;
-                scaled down for the larger configurations).
+                scaled down for the larger configurations); --no-cpu-baseline skips it
 """
 import argparse
 import json
@@ -213,7 +218,7 @@ def launch_ranks(n):
     return rc
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)    # >= 20 warm-up + >= 100 timed steps
@@ -222,15 +227,23 @@ def main():
     ap.add_argument("--lr", type=float, default=None,
                     help="Adam step size (default 1e-5: at the reference's 5e-4, leomed_mimic_config.json:20, the reference "
                          "arithmetic itself diverges on uniform-random images, profiles/r02_oracle_lr_divergence.txt)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs), also measure the host cost of one step call, the "
+                         "roofline pass and the CPU baseline; a plain run leaves them null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (loss terms, latents, "
                          "reconstructions) as DIR/<name>.npy in float32, at most 64 MB in all: arrays "
                          "too large for that are written as a fixed, seeded sample of their elements (rank 0)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
@@ -375,17 +388,19 @@ def main():
     # host cost of ONE step call with an idle queue in front of it (outside the timed region).  The time the host needs
     # to enqueue K back-to-back steps (host_enqueue_ms_per_step) mostly measures back-pressure from the GPU queue: it
     # tracks the GPU's step time whatever the host's own cost is.
-    host_call = []
-    for i in range(3):
-        torch.cuda.synchronize()
-        th = time.perf_counter()
-        run(1, start=args.warmup + args.steps + i)
-        host_call.append((host_done[0] - th) * 1e3)
-    fence()
-    host_call_ms = sorted(host_call)[1]
+    host_call_ms = None
+    if args.full:
+        host_call = []
+        for i in range(3):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            run(1, start=args.warmup + args.steps + i)
+            host_call.append((host_done[0] - th) * 1e3)
+        fence()
+        host_call_ms = sorted(host_call)[1]
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # second pass of the same steps, eager and on ONE stream, with HIP events around every implicit-GEMM launch:
         # inside the replayed graph single kernels cannot be bracketed, and with the side streams on a kernel's
         # events would also time whatever runs beside it.  (profiles/ holds the rocprofv3 stats of both regimes.)
@@ -469,7 +484,7 @@ def main():
                                              "per_kernel_ms_per_step": {k: round(v[1] / nprof, 3) for k, v in prof.items()}}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.config)
 
     if hist and rank == 0:
@@ -493,7 +508,7 @@ def main():
                                    + ", BatchNorm batch stats + dropout, Adam",
                        "global_batch": bsz * world, "parallelism": f"dp{world}",
                        "elbo_iters_per_sec": round(args.steps / elapsed, 3),
-                       "host_ms_per_step_call_idle_queue": round(host_call_ms, 3),
+                       "host_ms_per_step_call_idle_queue": round(host_call_ms, 3) if host_call_ms is not None else None,
                        "host_enqueue_ms_per_step": round(host_ms, 3), "hip_graph": bool(use_graph),
                        # launch plans: the committed table (mimic_amd/plans_gfx950.json) or the in-process tuner
                        "launch_plans": ops.plan_source_summary(),

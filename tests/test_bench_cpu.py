@@ -1,5 +1,5 @@
 """bench.py --dump-outputs on CPU: the files stay within the 64 MB budget, small arrays are written whole, large ones as
-the same seeded sample on every run."""
+the same seeded sample on every run; the extra measurements are behind --full."""
 import os
 
 import numpy as np
@@ -41,6 +41,16 @@ def test_dump_fits_the_budget_at_the_default_size(tmp_path):
     arrays = {f"a{i}": torch.zeros(n) for i, n in enumerate([1, 100, 10 ** 5, 10 ** 7, 3 * 10 ** 7])}
     bench.write_outputs(arrays, str(tmp_path))
     assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 * 10 ** 6
+
+
+def test_full_is_off_by_default():
+    """a plain run measures only the headline; the roofline pass, the CPU baseline and the host-cost steps need --full"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and (plain.steps, plain.warmup, plain.dump_outputs) == (5, 2, None)
+    full = bench.parse_args(["--full", "--no-cpu-baseline"])
+    assert full.full is True and full.no_cpu_baseline is True and full.no_roofline is False
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
 
 
 def _one_step_outputs(monkeypatch):

@@ -1,5 +1,6 @@
-"""bench.py's output contract on the GPU (one short run per storage family): one JSON line with the driver's keys, the
-roofline object measured live, no CPU baseline when asked not to."""
+"""bench.py's output contract on the GPU (one short --full run per storage family): one JSON line with the driver's keys,
+the roofline object measured live, no CPU baseline when asked not to; a plain run: the same line with the extra
+measurements left null."""
 import json
 import os
 import subprocess
@@ -16,8 +17,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line(cfg, dtype, bound, tmp_path):
     dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", cfg, "--steps", "4", "--warmup", "2",
-                          "--no-cpu-baseline", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600,
-                         cwd=REPO)
+                          "--full", "--no-cpu-baseline", "--dump-outputs", str(dump)], capture_output=True, text=True,
+                         timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -40,3 +41,21 @@ def test_bench_line(cfg, dtype, bound, tmp_path):
     assert loss == pytest.approx(line["config"]["last_total_loss"], rel=1e-6)
     for f in files:
         assert np.isfinite(np.load(dump / f)).all(), f
+
+
+def test_plain_bench_line(tmp_path):
+    """a plain run (no --full): the headline fields and --dump-outputs as in a --full run, no roofline pass, no CPU baseline
+    and no host-cost steps"""
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "2",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "samples/sec" and line["unit"] == "samples/sec" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["steps"] == 4 and line["warmup"] == 2 and line["value"] > 0
+    assert abs(line["value"] - line["config"]["global_batch"] / line["ms_per_step"] * 1e3) <= 0.01 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert line["config"]["host_ms_per_step_call_idle_queue"] is None and line["config"]["hip_graph"] is True
+    files = os.listdir(dump)
+    assert "total_loss.npy" in files and "rec.text.logits.npy" in files
+    assert float(np.load(dump / "total_loss.npy")) == pytest.approx(line["config"]["last_total_loss"], rel=1e-6)
