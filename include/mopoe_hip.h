@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPOE_ABI_VERSION 21
+#define MOPOE_ABI_VERSION 22
 
 /* error codes */
 #define MOPOE_OK 0
@@ -411,6 +411,24 @@ int mopoe_token_softmax_grad_logits(const void* logits, int32_t is_bf16, const f
                                     int64_t rows, int32_t V, float norm, void* dx, void* stream);
 int mopoe_dense_logprob_rows(const float* logp, const float* target, int64_t rows, int64_t per_row,
                              int64_t target_rows, float* out, void* stream);
+
+/* Importance-sampled likelihood estimates of the factorized representation (mimic/evaluation/eval_metrics/likelihood.py:17-96,
+ * mimic/utils/likelihood.py:13-220; evaluation only, fp32).  Rows are sample-major: r = k B + b, R = K B.
+ *   mopoe_lhood_style_sample: mu / logvar [B, D] (the subset posterior, not repeated), eps [K, B, D]; style_mu / style_logvar
+ *       [B, S] (one style source) and style_eps [K, B, S] ->
+ *       zcat [R, S + D] = [style_eps * exp(0.5 style_logvar) + style_mu | eps * exp(0.5 logvar) + mu] (the decoders' input),
+ *       t_c [R] = sum log N(z; 0, I) - sum log N(z; mu, logvar) over the D content columns, t_s [R] the same over S.
+ *   mopoe_lhood_estimates: lp[3] [R] = log p(x_m | z) per row (PA, Lateral, text: the *_logprob_rows kernels), t_c [R],
+ *       t_s [R] or NULL (no style term), subset_mask: bit m set when modality m is a subset member ->
+ *       out[4] = the PA, Lateral and text marginals and the joint, each mean_i log-mean-exp_k w[i K + k] over the reference's
+ *       (batch_size, K) view of the sample-major weights, with
+ *         marginal m: w = lp[m] + t_c + (bit m of subset_mask ? t_s : 0),   joint: w = lp[0] + lp[1] + lp[2] + t_c + 3 t_s.
+ *       Deterministic (one workgroup per estimate, fixed-order sums, no atomics). */
+int mopoe_lhood_style_sample(const float* mu, const float* logvar, const float* eps, const float* style_mu,
+                             const float* style_logvar, const float* style_eps, int32_t K, int32_t B, int32_t D, int32_t S,
+                             float* zcat, float* t_c, float* t_s, void* stream);
+int mopoe_lhood_estimates(const float* const lp[3], const float* t_c, const float* t_s, int32_t K, int32_t B,
+                          int32_t subset_mask, float* out, void* stream);
 
 /* ---- embedding (word_encoding/mmvae_text_enc.py:27-28,73) ------------------------------------------
  * out[r, :] = table[(int)ids[r], :]; backward scatter-adds into dtable (overwritten), skipping

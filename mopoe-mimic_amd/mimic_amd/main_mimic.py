@@ -56,6 +56,8 @@ def _worker(rank: int, flags: argparse.Namespace, result_path: str) -> None:
 
 class Main:
     def __init__(self, flags: argparse.Namespace, testing: bool = False):
+        from .utils.experiment import check_flags
+        check_flags(flags)      # (in this process: a bad combination must not wait for the first evaluation epoch)
         self.flags = flags
         self.max_tries = 10       # maximum restarts of the experiment due to nan values (main_mimic.py:36-38)
         self.current_tries = 0
@@ -138,11 +140,20 @@ def parse_flags(argv=None) -> argparse.Namespace:
     return get_method(base)   # (--method picks the objective, as mimic/main_mimic.py does through get_method)
 
 
+def result_line(history) -> dict:
+    """the launcher's final JSON line; 'last_lhoods' only when --calc_nll computed an estimate"""
+    last = history[-1]
+    result = {"epochs": len(history), "last_test_loss": last["test"].get("total_loss"),
+              "graphed_steps_last_epoch": last["train"].get("graphed_steps")}
+    lhoods = [h["test"]["lhoods"] for h in history if "lhoods" in h["test"]]
+    if lhoods:
+        result["last_lhoods"] = lhoods[-1]
+    return result
+
+
 if __name__ == "__main__":
     m = Main(parse_flags())
     ok = m.main()
     if m.history:
-        last = m.history[-1]
-        print(json.dumps({"epochs": len(m.history), "last_test_loss": last["test"].get("total_loss"),
-                          "graphed_steps_last_epoch": last["train"].get("graphed_steps")}))
+        print(json.dumps(result_line(m.history)))
     sys.exit(0 if ok is True else 1)

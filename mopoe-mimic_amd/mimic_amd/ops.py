@@ -20,7 +20,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOPOE_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libmopoe_hip.so")  # env override: A/B builds
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 RES_A, RES_B = 2.0, 0.3
 BN_EPS = 1e-5
@@ -1230,6 +1230,37 @@ def dense_logprob_rows(logp, target):
     assert target[0].numel() == per_row and rows % tb == 0
     out = torch.empty(rows, dtype=torch.float32, device=logp.device)
     _check(lib().mopoe_dense_logprob_rows(_p(logp), _p(target), C.c_int64(rows), C.c_int64(per_row), C.c_int64(tb), _p(out), _stream()))
+    return out
+
+
+def lhood_style_sample(mu, logvar, eps, style_mu, style_logvar, style_eps):
+    """factorized likelihood estimator, one subset: mu / logvar [B,D], eps [K,B,D]; style_mu / style_logvar [B,S],
+    style_eps [K,B,S] -> zcat [K*B, S+D] = [z_style | z] (row k*B + b), t_c [K*B], t_s [K*B] (log N(z;0,I) - log q(z))"""
+    _dev(mu, logvar, eps, style_mu, style_logvar, style_eps)
+    b, d = mu.shape
+    s = style_mu.shape[1]
+    k = eps.shape[0]
+    if (logvar.shape != mu.shape or tuple(eps.shape) != (k, b, d) or tuple(style_mu.shape) != (b, s)
+            or style_logvar.shape != style_mu.shape or tuple(style_eps.shape) != (k, b, s)):
+        raise MopoeHipError("lhood_style_sample: mu/logvar [B,D], eps [K,B,D], style_mu/style_logvar [B,S], style_eps [K,B,S]")
+    zcat = torch.empty(k * b, s + d, dtype=torch.float32, device=mu.device)
+    t_c = torch.empty(k * b, dtype=torch.float32, device=mu.device)
+    t_s = torch.empty_like(t_c)
+    _check(lib().mopoe_lhood_style_sample(_p(mu), _p(logvar), _p(eps), _p(style_mu), _p(style_logvar), _p(style_eps),
+                                          k, b, d, s, _p(zcat), _p(t_c), _p(t_s), _stream()))
+    return zcat, t_c, t_s
+
+
+def lhood_estimates(lp, t_c, t_s, n_samples: int, subset_mask: int):
+    """lp: 3-list (PA, Lateral, text) of per-row log p(x_m|z) [K*B]; t_c [K*B]; t_s [K*B] or None; subset_mask: bit m for
+    a subset member -> float [4]: the three marginal estimates and the joint"""
+    _dev(*lp, t_c, t_s)
+    r = t_c.shape[0]
+    if r % n_samples or any(t.shape != (r,) for t in (*lp, t_c) + ((t_s,) if t_s is not None else ())):
+        raise MopoeHipError("lhood_estimates: every per-row vector must be [K*B]")
+    out = torch.empty(4, dtype=torch.float32, device=t_c.device)
+    _check(lib().mopoe_lhood_estimates(_ptr3(lp), _p(t_c), _p(t_s), int(n_samples), r // int(n_samples), int(subset_mask),
+                                       _p(out), _stream()))
     return out
 
 

@@ -442,6 +442,34 @@ def test(epoch, exp, test_loader, max_steps=None):
     return {k: v / max(n, 1) for k, v in out.items()}
 
 
+LHOOD_BATCH_SIZE = 30
+
+
+def estimate_test_likelihoods(exp, epoch):
+    """--calc_nll at an evaluation epoch (run_epochs.py:186-213): the importance-sampled likelihood estimates of every
+    subset over the test split at batch size 30, {subset: {PA, Lateral, text, joint}}; None (and a message) when the
+    split has fewer than 30 rows.  Every rank estimates on its own device (no collective).  flags.batch_size is 30 only
+    for the estimate and restored afterwards, so the captured train step replays at the training batch size."""
+    from torch.utils.data import DataLoader
+    from .dataio.utils import PrefetchToDevice
+    from .evaluation.eval_metrics.likelihood import estimate_likelihoods
+    flags = exp.flags
+    training_batch_size = flags.batch_size
+    flags.batch_size = LHOOD_BATCH_SIZE
+    try:
+        # (after the batch size is set: Mimic_testing's length is testing_batches * flags.batch_size)
+        n = len(exp.dataset_test)
+        if n < LHOOD_BATCH_SIZE:
+            print(f"epoch {epoch}: likelihood estimate skipped: the test split has {n} rows, fewer than one batch of "
+                  f"{LHOOD_BATCH_SIZE}", flush=True)
+            return None
+        loader = DataLoader(exp.dataset_test, batch_size=LHOOD_BATCH_SIZE, shuffle=True,
+                            num_workers=getattr(flags, "dataloader_workers", 0), drop_last=True)
+        return estimate_likelihoods(exp, PrefetchToDevice(loader, flags.device))
+    finally:
+        flags.batch_size = training_batch_size
+
+
 class Callbacks:
     """Hot-path subset of the reference's Callbacks (mimic/utils/experiment.py:286-402): ReduceLROnPlateau on the test
     loss, the early-stopping bookkeeping and the checkpoint rule (every 50 epochs and at end_epoch, rank 0 only:
@@ -549,6 +577,10 @@ def run_epochs(rank, exp) -> typing.List[dict]:
         if reducer is not None:
             reducer.sync_buffers()       # running statistics are per rank during training; rank 0's are evaluated / saved
         test_results = test(epoch, exp, test_loader if resident else PrefetchToDevice(test_loader, args.device))
+        if getattr(args, "calc_nll", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
+            lhoods = estimate_test_likelihoods(exp, epoch)
+            if lhoods is not None:
+                test_results["lhoods"] = lhoods
         history.append({"epoch": epoch, "train": tr, "test": test_results, "seconds": time.time() - end})
         if callbacks.update_epoch(epoch, test_results, time.time() - end):
             break

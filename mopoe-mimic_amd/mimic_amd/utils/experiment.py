@@ -30,6 +30,7 @@ def default_flags(**overrides) -> argparse.Namespace:
         div_weight_m3_content=0.25, rec_weight_m1=0.33, rec_weight_m2=0.33, rec_weight_m3=0.33,
         initial_learning_rate=5e-4, beta_1=0.9, beta_2=0.999, dataset="testing", distributed=False,
         steps_per_training_epoch=0, seed=0,
+        calc_nll=False,   # importance-sampled likelihood estimates at every eval_freq-th and the last epoch (run_epochs.py:190-213)
         # (evaluated only when the caller passes no device: a launcher process must not initialise the GPU)
         device=overrides["device"] if "device" in overrides else torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         start_epoch=0, end_epoch=1, eval_freq=10, world_size=1, dataloader_workers=0, weighted_sampler=False,
@@ -48,10 +49,18 @@ def default_flags(**overrides) -> argparse.Namespace:
 from ..dataio.utils import get_str_labels  # noqa: E402
 
 
+def check_flags(flags):
+    """flag combinations that would fail only at the first evaluation epoch, refused before any training"""
+    if getattr(flags, "calc_nll", False) and getattr(flags, "factorized_representation", False):
+        from ..evaluation.eval_metrics.likelihood import check_style_dims
+        check_style_dims(flags)
+
+
 class HotPathExperiment:
     """Carries exactly what run_epochs.basic_routine_epoch / train read from the experiment object."""
 
     def __init__(self, flags):
+        check_flags(flags)
         self.flags = flags
         self.dataset = flags.dataset
         self.labels = get_str_labels(getattr(flags, "binary_labels", False))
