@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPOE_ABI_VERSION 22
+#define MOPOE_ABI_VERSION 23
 
 /* error codes */
 #define MOPOE_OK 0
@@ -429,6 +429,28 @@ int mopoe_lhood_style_sample(const float* mu, const float* logvar, const float* 
                              float* zcat, float* t_c, float* t_s, void* stream);
 int mopoe_lhood_estimates(const float* const lp[3], const float* t_c, const float* t_s, int32_t K, int32_t B,
                           int32_t subset_mask, float* out, void* stream);
+
+/* Latent-representation evaluation (--eval_lr; mimic/evaluation/eval_metrics/representation.py:147-187; evaluation only, fp32):
+ * the reference's LogisticRegression(random_state=0, solver='lbfgs', max_iter=1000) per (modality subset, label), restated
+ * as the problem sklearn's defaults pose -- with y in {0, 1} and the intercept b NOT penalised
+ *     f(w, b) = C sum_i [ log(1 + exp(m_i)) - y_i m_i ] + 1/2 |w|^2,   m_i = x_i . w + b
+ * -- and solved to its (unique) optimum instead of to lbfgs' stopping point.
+ *   mopoe_logreg_fit: X [S, N, D] (one data matrix per subset, shared by its L labels), Y [N, L] (1 where > 0.5, else 0) ->
+ *       W [S, L, D + 1] (D coefficients, then the intercept) and info [S, L, 2] = (Newton steps taken, |grad f|_inf at W).
+ *       ALL S * L problems in ONE launch: one workgroup per problem runs the whole damped-Newton loop (Hessian as a packed
+ *       lower triangle in LDS, Cholesky, backtracking on f), at most max_iter steps; it stops as soon as |grad f|_inf <= tol,
+ *       or when a full step no longer changes f within float resolution and does not lower |grad f|_inf (tol is then
+ *       below what float32 reaches: compare info with tol).  Returns on any input -- every loop is bounded, NaN ends it --
+ *       and reports non-convergence through info only.  Deterministic (fixed-order sums, no atomics).
+ *       MOPOE_ERR_ARG: D > 256 (the triangle of D + 1 no longer fits one workgroup's LDS), N < 2, L < 1, S < 1, C <= 0.
+ *       A label column with a single class has no finite optimum in b: the caller checks that (mimic_amd raises ValueError).
+ *   mopoe_logreg_predict: x = HOST array of S <= 8 device pointers, each [M, D] (a batch's subset means go in as they are),
+ *       W as above -> pred [S, M, L] = 1 where x . w + b > 0 else 0 (LogisticRegression.predict), and, when dec != NULL,
+ *       the decision values x . w + b [S, M, L]. */
+int mopoe_logreg_fit(const float* X, const float* Y, int32_t S, int32_t N, int32_t D, int32_t L, float C, int32_t max_iter,
+                     float tol, float* W, float* info, void* stream);
+int mopoe_logreg_predict(const float* const* x, int32_t S, int32_t M, int32_t D, int32_t L, const float* W, float* pred,
+                         float* dec, void* stream);
 
 /* ---- embedding (word_encoding/mmvae_text_enc.py:27-28,73) ------------------------------------------
  * out[r, :] = table[(int)ids[r], :]; backward scatter-adds into dtable (overwritten), skipping

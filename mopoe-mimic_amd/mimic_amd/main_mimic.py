@@ -141,13 +141,17 @@ def parse_flags(argv=None) -> argparse.Namespace:
 
 
 def result_line(history) -> dict:
-    """the launcher's final JSON line; 'last_lhoods' only when --calc_nll computed an estimate"""
+    """the launcher's final JSON line; 'last_lhoods' only when --calc_nll computed an estimate, 'last_lr_eval' only when
+    --eval_lr evaluated the latent representation"""
     last = history[-1]
     result = {"epochs": len(history), "last_test_loss": last["test"].get("total_loss"),
               "graphed_steps_last_epoch": last["train"].get("graphed_steps")}
     lhoods = [h["test"]["lhoods"] for h in history if "lhoods" in h["test"]]
     if lhoods:
         result["last_lhoods"] = lhoods[-1]
+    lr_evals = [h["test"]["lr_eval"] for h in history if "lr_eval" in h["test"]]
+    if lr_evals:
+        result["last_lr_eval"] = lr_evals[-1]
     return result
 
 

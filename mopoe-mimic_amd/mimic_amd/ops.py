@@ -20,7 +20,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOPOE_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libmopoe_hip.so")  # env override: A/B builds
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 RES_A, RES_B = 2.0, 0.3
 BN_EPS = 1e-5
@@ -1262,6 +1262,42 @@ def lhood_estimates(lp, t_c, t_s, n_samples: int, subset_mask: int):
     _check(lib().mopoe_lhood_estimates(_ptr3(lp), _p(t_c), _p(t_s), int(n_samples), r // int(n_samples), int(subset_mask),
                                        _p(out), _stream()))
     return out
+
+
+def logreg_fit(x, y, c: float = 1.0, max_iter: int = 100, tol: float = 1e-5):
+    """x [S, N, D] float (one data matrix per subset), y [N, L] float 0/1 -> (W [S, L, D+1] coefficients then intercept,
+    info [S, L, 2] = (Newton steps, |grad f|_inf at W)): the optimum of sklearn's LogisticRegression(C=c) problem per
+    (subset, label), all S * L fits in one launch.  A problem has converged when info[..., 1] <= tol; the default tol sits
+    at what float32 reaches, and a fit that cannot reach it stops where float32 stops improving."""
+    _dev(x, y)
+    if (x.dim() != 3 or y.dim() != 2 or y.shape[0] != x.shape[1] or x.dtype != torch.float32 or y.dtype != torch.float32
+            or y.device != x.device):
+        raise MopoeHipError("logreg_fit: x [S,N,D] float32 and y [N,L] float32 on one device")
+    s, n, d = x.shape
+    l = y.shape[1]
+    w = torch.empty(s, l, d + 1, dtype=torch.float32, device=x.device)
+    info = torch.empty(s, l, 2, dtype=torch.float32, device=x.device)
+    _check(lib().mopoe_logreg_fit(_p(x), _p(y), s, n, d, l, C.c_float(c), int(max_iter), C.c_float(tol), _p(w), _p(info),
+                                  _stream()))
+    return w, info
+
+
+def logreg_predict(x, w, want_decision: bool = False):
+    """x: [S, M, D] tensor or a sequence of S tensors [M, D]; w [S, L, D+1] -> pred [S, M, L] (1.0 where x . w + b > 0),
+    and the decision values [S, M, L] when want_decision"""
+    xs = list(x.unbind(0)) if isinstance(x, torch.Tensor) else list(x)
+    _dev(w, *xs)
+    if (w.dim() != 3 or len(xs) != w.shape[0] or len(xs) > 8 or w.dtype != torch.float32
+            or any(t.dim() != 2 or t.shape != xs[0].shape or t.shape[1] + 1 != w.shape[2] or t.dtype != torch.float32
+                   or t.device != w.device for t in xs)):
+        raise MopoeHipError("logreg_predict: S <= 8 float32 matrices [M,D] and w [S,L,D+1] float32 on one device")
+    s, l = w.shape[0], w.shape[1]
+    m, d = xs[0].shape
+    pred = torch.empty(s, m, l, dtype=torch.float32, device=w.device)
+    dec = torch.empty_like(pred) if want_decision else None
+    ptrs = (C.c_void_p * s)(*[t.data_ptr() for t in xs])
+    _check(lib().mopoe_logreg_predict(ptrs, s, m, d, l, _p(w), _p(pred), _p(dec), _stream()))
+    return (pred, dec) if want_decision else pred
 
 
 def embedding_fwd(ids, table, out_dtype=None):

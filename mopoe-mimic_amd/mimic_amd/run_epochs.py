@@ -470,6 +470,25 @@ def estimate_test_likelihoods(exp, epoch):
         flags.batch_size = training_batch_size
 
 
+def evaluate_latent_representation(exp, epoch):
+    """--eval_lr at an evaluation epoch (run_epochs.py:186-188, :202-213): logistic-regression classifiers per label and per
+    subset, fitted on the subset means of flags.num_training_samples_lr training rows and scored on the test split ->
+    {subset: {metric: value}}.  flags.batch_size is 30 only for the evaluation (the reference sets it for all of its
+    evaluation hooks) and restored afterwards, whatever happens, so the captured train step replays at the training batch
+    size; the model's train/eval mode comes back as well.  Every rank evaluates on its own device (no collective)."""
+    from .evaluation.eval_metrics.representation import (LR_BATCH_SIZE, test_clf_lr_all_subsets,
+                                                         train_clf_lr_all_subsets)
+    flags = exp.flags
+    training_batch_size, was_training = flags.batch_size, exp.mm_vae.training
+    flags.batch_size = LR_BATCH_SIZE
+    try:
+        clf_lr = train_clf_lr_all_subsets(exp)
+        return test_clf_lr_all_subsets(clf_lr, exp)
+    finally:
+        flags.batch_size = training_batch_size
+        exp.mm_vae.train(was_training)
+
+
 class Callbacks:
     """Hot-path subset of the reference's Callbacks (mimic/utils/experiment.py:286-402): ReduceLROnPlateau on the test
     loss, the early-stopping bookkeeping and the checkpoint rule (every 50 epochs and at end_epoch, rank 0 only:
@@ -577,6 +596,8 @@ def run_epochs(rank, exp) -> typing.List[dict]:
         if reducer is not None:
             reducer.sync_buffers()       # running statistics are per rank during training; rank 0's are evaluated / saved
         test_results = test(epoch, exp, test_loader if resident else PrefetchToDevice(test_loader, args.device))
+        if getattr(args, "eval_lr", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
+            test_results["lr_eval"] = evaluate_latent_representation(exp, epoch)
         if getattr(args, "calc_nll", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
             lhoods = estimate_test_likelihoods(exp, epoch)
             if lhoods is not None:

@@ -31,6 +31,9 @@ def default_flags(**overrides) -> argparse.Namespace:
         initial_learning_rate=5e-4, beta_1=0.9, beta_2=0.999, dataset="testing", distributed=False,
         steps_per_training_epoch=0, seed=0,
         calc_nll=False,   # importance-sampled likelihood estimates at every eval_freq-th and the last epoch (run_epochs.py:190-213)
+        # latent-representation evaluation at the same epochs (run_epochs.py:202-213): classifiers on the subset means of
+        # num_training_samples_lr training rows (mimic/utils/BaseFlags.py)
+        eval_lr=False, num_training_samples_lr=500,
         # (evaluated only when the caller passes no device: a launcher process must not initialise the GPU)
         device=overrides["device"] if "device" in overrides else torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         start_epoch=0, end_epoch=1, eval_freq=10, world_size=1, dataloader_workers=0, weighted_sampler=False,
