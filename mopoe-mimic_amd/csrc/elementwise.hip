@@ -542,11 +542,13 @@ template <typename T>
 static int colsum_t(const T* x, float* out, int64_t rows, int32_t C, int32_t out_is_zero, void* stream) {
   EW_ARGCHECK(x && out && rows > 0 && C > 0, "colsum: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  if (!out_is_zero && hipMemsetAsync(out, 0, sizeof(float) * C, st) != hipSuccess) { set_error("colsum memset failed"); return MOPOE_ERR_LAUNCH; }
   int rc;
   constexpr int W = EwVec<T>::wide;
+  const bool wide = ew_wide_ok<T>(C, {x}, "colsum", &rc);
+  if (!wide && !std::is_same<T, float>::value) return rc;   // refused before anything is enqueued: `out` is not even zero-filled
+  if (!out_is_zero && hipMemsetAsync(out, 0, sizeof(float) * C, st) != hipSuccess) { set_error("colsum memset failed"); return MOPOE_ERR_LAUNCH; }
 #define MOPOE_L(U_) hipLaunchKernelGGL((colsum_kernel<T, W, U_>), dim3(ew_grid(rows, C, W)), dim3(EW_THREADS), 0, st, x, out, (long)rows, C)
-  if (ew_wide_ok<T>(C, {x}, "colsum", &rc)) { EW_DISPATCH_U(MOPOE_L) }
+  if (wide) { EW_DISPATCH_U(MOPOE_L) }
 #undef MOPOE_L
   else if constexpr (std::is_same<T, float>::value)
     hipLaunchKernelGGL((colsum_kernel<float, 1, 1>), dim3(ew_grid(rows, C, 1)), dim3(EW_THREADS), 0, st, x, out, (long)rows, C);
