@@ -7,7 +7,11 @@
 Each configuration runs in a fresh child process (one GPU user at a time): the model of bench.py, train mode with dropout,
 the tuner forced on (MOPOE_AUTOTUNE=force: the committed table is ignored) with longer timing batches than the in-process
 default, two eager train steps (every (op, geometry, fusion) triple of a step is met in the first), then the tuner's table is
-dumped.  The parent merges the children's tables; a triple two configurations share keeps the first one's plan."""
+dumped.  The parent merges the children's tables; a triple two configurations share keeps the first one's plan.
+
+Before a new table is committed, run the kernel-level tests against it: MOPOE_PLAN_TABLE=<file> makes
+tests/test_plan_table_cpu.py and tests/test_plan_table_gpu.py read that file (ops.PLAN_TABLE_PATH) instead of the committed
+one -- every plan at its own layer geometry against fp64, element by element."""
 import argparse
 import json
 import os

@@ -7,7 +7,10 @@ time and keep a change only if the replayed train step (one hipGraph, three netw
 
 The isolated timings that built the table (tests/tools/make_plan_table.py) rank a plan by its own duration (x the share of the
 chip it occupies); what a plan costs the STEP also depends on what runs beside it.  Greedy, one triple at a time, most expensive
-first; a candidate is accepted when the step is faster by more than --gain (default 0.3 %) in two consecutive measurements."""
+first; a candidate is accepted when the step is faster by more than --gain (default 0.3 %) in two consecutive measurements.
+
+A refined table is checked like a measured one before it is committed: MOPOE_PLAN_TABLE=<file> runs
+tests/test_plan_table_cpu.py and tests/test_plan_table_gpu.py on it (ops.PLAN_TABLE_PATH)."""
 import argparse
 import gc
 import json
