@@ -110,7 +110,12 @@ size_t mopoe_conv_workspace_bytes(void);
  *          | 16..19 = tiles 12..15 with the fp32 products computed on the bf16 matrix pipe: each fp32 operand value is split
  *            EXACTLY into three bf16 parts in registers (a = h + m + l) and six of the nine partial products (all but m l, l m, l l,
  *            each below 2^-24 |a b|) are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 -- results within fp32 rounding of the
- *            fp32-MFMA tiles', measured closer to fp64 than theirs; plain operand forms only (no BN -> ReLU on load); 19 has 3 buffers
+ *            fp32-MFMA tiles', measured closer to fp64 than theirs; plain operand forms only (no BN -> ReLU on load); 19 has 3 buffers.
+ *            Kernel template arguments <BM, BN, WGM, WGN, spec, buffers, WGK, 1>:
+ *              16 = <128, 128, 2, 2, ., 2, 1, 1>   17 = <128, 64, 2, 1, ., 3, 2, 1>   18 = <64, 64, 2, 1, ., 4, 2, 1>
+ *              19 = <256, 128, 4, 2, ., 3, 1, 1>.  WGK = 2 (17, 18): the block's four waves are 2 (M) x 1 (N) x 2 (K) -- a wave owns a
+ *              64- (32-) row x 64-column sub-tile over one 16-k half of every 32-deep chunk, and the two waves of a pair add their
+ *              accumulators through LDS once per M tile; block shape, stages and epilogue are those of 2 x 2 waves
  *   split  0 auto | n >= 1 blocks sharing one tile's tap x channel reduction, finished by the last-arriving block (needs workspace)
  * fp32 weight gradient (mopoe_conv_wgrad):
  *   tile  -1 auto | 0 = 128x128 | 2 = 64x64 (Cin x Cout tile of one tap, register-staged, 16 pixels per chunk)
@@ -568,7 +573,8 @@ int mopoe_adam_step(const mopoe_adam_seg* segs, int32_t nseg, float* step, const
  *   122..123 wgrad_parity_bf16_kernel (tiles 8 / 9: four taps per block), S tile 64 / 128
  *   124..126 pw_front_fwd_bf16_kernel<64, false> (statistics pass), <64, true> (a2 pass), pw_front_bwd_bf16_kernel<64>
  *   127..129 pw_front_fwd_f32_kernel<false>, <true>, pw_front_bwd_f32_kernel
- *   130..137 gather_gemm_f32_glds_kernel<..., EMU = 1> (fp32 tiles 16..19): (tile - 16) * 2 + (input gradient ? 1 : 0)
+ *   130..137 gather_gemm_f32_glds_kernel<..., WGK, EMU = 1> (fp32 tiles 16..19; WGK = 2 for 17 and 18, see mopoe_conv_plan):
+ *            (tile - 16) * 2 + (input gradient ? 1 : 0)
  *   138..139 wgrad_gemm_f32_glds_kernel<..., EMU = 1> (fp32 wgrad tiles 7, 8)
  *   140..143 wgrad_parity_f32_kernel<CS, conv ? true : false> (fp32 wgrad tiles 9 / 10): (CS == 128 ? 2 : 0) + (transposed ? 1 : 0) */
 #define MOPOE_PROF_KINDS 144

@@ -1237,18 +1237,18 @@ static int launch_gather(const float* X, const float* W, const float* bias, floa
     if (spec == 1) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 1, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a); \
     else hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 3, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a);          \
   } while (0)
-#define MOPOE_LAUNCH_GLDS_EMU(BM_, BN_, WM_, WN_, ST_)                                                                                   \
+#define MOPOE_LAUNCH_GLDS_EMU(BM_, BN_, WM_, WN_, ST_, WK_)                                                                              \
   do {                                                                                                                                \
-    if (spec == 1) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 1, ST_, 1>), grid, dim3(64 * WM_ * WN_), 0, stream, a); \
-    else hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 3, ST_, 1>), grid, dim3(64 * WM_ * WN_), 0, stream, a);          \
+    if (spec == 1) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 1, ST_, WK_, 1>), grid, dim3(64 * WM_ * WN_ * WK_), 0, stream, a); \
+    else hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 3, ST_, WK_, 1>), grid, dim3(64 * WM_ * WN_ * WK_), 0, stream, a);          \
   } while (0)
     if (emu) {
-      // (the two wide tiles: one 4-wave block per CU -- 512 registers per wave for the software pipeline -- and the LDS that frees
-      // spent on stages: 4 x 32 KB, 3 x 48 KB)
-      if (cfg == 12) MOPOE_LAUNCH_GLDS_EMU(128, 128, 2, 2, 2);
-      else if (cfg == 13) MOPOE_LAUNCH_GLDS_EMU(128, 64, 2, 2, 3);
-      else if (cfg == 14) MOPOE_LAUNCH_GLDS_EMU(64, 64, 2, 2, 4);
-      else MOPOE_LAUNCH_GLDS_EMU(256, 128, 4, 2, 3);
+      // (tiles 17 and 18, whose 2 x 2 waves would each split fragments a neighbour splits too, partition K instead: 2 x 1 x 2
+      // waves, conv_gemm_glds.inc, WGK.  Same block, same stages, same epilogue layout)
+      if (cfg == 12) MOPOE_LAUNCH_GLDS_EMU(128, 128, 2, 2, 2, 1);
+      else if (cfg == 13) MOPOE_LAUNCH_GLDS_EMU(128, 64, 2, 1, 3, 2);
+      else if (cfg == 14) MOPOE_LAUNCH_GLDS_EMU(64, 64, 2, 1, 4, 2);
+      else MOPOE_LAUNCH_GLDS_EMU(256, 128, 4, 2, 3, 1);
     }
 #undef MOPOE_LAUNCH_GLDS_EMU
     else if (cfg >= 12) {

@@ -35,6 +35,12 @@ __device__ __forceinline__ void lds_frag_f1(float& r, unsigned addr) {
   MOPOE_DEVICE_ASM("ds_read_b32 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
 }
 
+// four consecutive 1-KB rows of 16 bytes per lane (the accumulator exchange of the K-partitioned waves); valid on return
+__device__ __forceinline__ void lds_load_x4(u32x4& a, u32x4& b, u32x4& c, u32x4& d, unsigned addr) {
+  MOPOE_DEVICE_ASM("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+                   : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(addr) : "memory");
+}
+
 // ---- EMU: the fp32 products on the bf16 matrix pipe (round 4) ------------------------------------------------------------------
 // An fp32 number is the exact sum of three bf16 numbers: h = bf16(a), m = bf16(a - h), l = a - h - m (round-to-nearest-even
 // conversions; a - h has at most 16 significant bits and |a - h| <= 2^-8 |a|, a - h - m at most 8: l is exact).  The product of
@@ -138,13 +144,25 @@ __device__ __forceinline__ void pin_reg(T& r) { MOPOE_DEVICE_ASM("" : "+v"(r)); 
 //         stage are requested R iterations before they are transformed and written into the LDS buffer that has just become
 //         free (R = 1 with two buffers, R = 2 with four: the small tile of the deep layers needs more than one 0.5-us
 //         iteration to cover a load), and sit there NSTAGE - 1 further iterations like a DMA'd stage
+//   WGK: 1 = every wave of the block walks all of k; 2 = K-partitioned (EMU only): the block's waves are WGM x WGNK x 2, wave
+//         (wm, wnk, kh) owns the (BM / WGM) x (BN / WGNK) sub-tile over pair kh of every 32-deep chunk (super-steps 2 kh and
+//         2 kh + 1: 16 of the chunk's 32 k).  A fragment is then read from LDS and split by ONE wave instead of two.  After the K
+//         loop the two waves of a k pair exchange halves of their accumulators through LDS and add: the epilogue sees the layout
+//         of WGM x (2 WGNK) waves with wn = 2 wnk + kh (the names WGN, WN, TJ, wn below are the EPILOGUE's; the main loop's are
+//         KWN, KTJ, wnk)
 //   EMU: 0 = v_mfma_f32_32x32x2_f32; 1 = the same products on the bf16 matrix pipe (split3 above)
-template <int BM, int BN, int WGM, int WGN, int SPEC, int NSTAGE, int EMU = 0>
-__global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel(const GemmArgs a) {
+template <int BM, int BN, int WGM, int WGNK, int SPEC, int NSTAGE, int WGK = 1, int EMU = 0>
+__global__ __launch_bounds__(64 * WGM * WGNK * WGK, 2) void gather_gemm_f32_glds_kernel(const GemmArgs a) {
+  static_assert(WGK == 1 || (WGK == 2 && EMU == 1 && SPEC != 2), "K-partitioned waves: two k halves, split-bf16 products, plain operand");
+  // Two sets of names.  EPILOGUE layout (everything from the exchange on: gemm_epilogue_rows.inc, gemm_colstats_rows.inc, the
+  // staging patches, ecol / ncol): WGN, WN, TJ, wn.  MAIN LOOP (fragment offsets, accumulators, both chunk loops): KWN, KTJ,
+  // wnk, kh.  With WGK = 1 the two sets are equal.
+  constexpr int WGN = WGNK * WGK;                          // wave columns of the epilogue
   constexpr int NT = 64 * WGM * WGN, NW = NT / 64;
-  constexpr int WM = BM / WGM, WN = BN / WGN;
-  constexpr int TI = WM / 32, TJ = WN / 32;
-  static_assert(TI >= 1 && TJ >= 1 && TI <= 2 && TJ <= 2 && WM % 32 == 0 && WN % 32 == 0, "wave tile: one to four 32x32 MFMA tiles");
+  constexpr int WM = BM / WGM, WN = BN / WGN, KWN = BN / WGNK;
+  constexpr int TI = WM / 32, TJ = WN / 32, KTJ = KWN / 32;
+  static_assert(TI >= 1 && TJ >= 1 && TI <= 2 && KTJ <= 2 && WM % 32 == 0 && WN % 32 == 0, "wave tile: one to four 32x32 MFMA tiles");
+  static_assert(WGK == 1 || (TJ == 1 && KTJ == 2), "K-partitioned waves: the wave keeps one of its two tile columns");
   static_assert(SPEC >= 1 && SPEC <= 3, "SPEC");
   static_assert(NSTAGE >= 2 && NSTAGE <= 4 && (SPEC != 2 || NSTAGE == 2 || NSTAGE == 4), "two to four LDS buffers (two or four with BN on load)");
   constexpr int R = NSTAGE == 4 ? 2 : 1;                   // (xform) register sets = iterations a raw-row load is given
@@ -178,6 +196,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WGN, wn = wave % WGN;
+  const int wnk = wn / WGK, kh = wn % WGK;                 // main loop: wave column and k half
   unsigned lbx = blockIdx.x, lby = blockIdx.y, lbz = blockIdx.z;
   if (a.xcd_remap) {
     const unsigned inner = gridDim.y * gridDim.z;
@@ -223,6 +242,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
     epi[4][c] = (n < a.Cn && a.bias) ? a.bias[n] : 0.f;
   }
   __syncthreads();
+  // (epilogue names from here to the fragment offsets)
   constexpr int E_LPR = WN / 8, E_RPP = 64 / E_LPR, E_NPASS = 32 / E_RPP;
   const int c8 = lane % E_LPR, rsub = lane / E_LPR;
   const int ecol = wn * WN + c8 * 8;
@@ -250,26 +270,32 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
       voffB[i] = n < a.Cn ? ((unsigned)k * (unsigned)a.Cout_w + (unsigned)n) * 4u : OOB;
     }
   }
-  // ---- fragment read offsets (bytes from the stage base) -------------------------------------------------------------
+  // ---- fragment read offsets (bytes from the stage base; main-loop names: KWN, KTJ, wnk, kh) ---------------------------
   // K-contiguous fragment of super-step q: the lane's row, logical chunk 2 q + lhi
-  unsigned aoff[TI][4];
+  // (K-partitioned: entry q = 0, 1 is super-step 2 kh + q, the wave's own pair)
+  constexpr int NQ = 4 / WGK;
+  const int q0 = (WGK - 1) * 2 * kh;
+  unsigned aoff[TI][NQ];
 #pragma unroll
   for (int i = 0; i < TI; ++i) {
     const int r = wm * WM + i * 32 + l31;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) aoff[i][q] = (unsigned)r * 128u + (unsigned)(((2 * q + lhi) ^ ((r >> 1) & 7)) * 16);
+    for (int q = 0; q < NQ; ++q) aoff[i][q] = (unsigned)r * 128u + (unsigned)(((2 * (q0 + q) + lhi) ^ ((r >> 1) & 7)) * 16);
   }
-  unsigned boff[TJ][w_nk ? 4 : 1];
+  unsigned boff[KTJ][w_nk ? NQ : 1];
 #pragma unroll
-  for (int j = 0; j < TJ; ++j) {
+  for (int j = 0; j < KTJ; ++j) {
+    // K-partitioned: the wave's tile column j is column j ^ kh of the block, so that the column a wave KEEPS after the exchange
+    // (kh, the epilogue's wn) is acc[.][0] in every wave: a different address, not a different register
+    const int jc = WGK == 2 ? (j ^ kh) : j;
     if (w_nk) {
-      const int r = wn * WN + j * 32 + l31;
+      const int r = wnk * KWN + jc * 32 + l31;
 #pragma unroll
-      for (int q = 0; q < (w_nk ? 4 : 1); ++q)
-        boff[j][q] = (unsigned)A_BYTES + (unsigned)r * 128u + (unsigned)(((2 * q + lhi) ^ ((r >> 1) & 7)) * 16);
+      for (int q = 0; q < (w_nk ? NQ : 1); ++q)
+        boff[j][q] = (unsigned)A_BYTES + (unsigned)r * 128u + (unsigned)(((2 * (q0 + q) + lhi) ^ ((r >> 1) & 7)) * 16);
     } else {
       // K-strided: k row 8 q + 4 lhi + e (immediate offset (8 q + e) * B_ROWB), column of the lane
-      boff[j][0] = (unsigned)A_BYTES + (unsigned)(4 * lhi) * (unsigned)B_ROWB + (unsigned)(wn * WN + j * 32 + l31) * 4u;
+      boff[j][0] = (unsigned)A_BYTES + (unsigned)(8 * q0 + 4 * lhi) * (unsigned)B_ROWB + (unsigned)(wnk * KWN + jc * 32 + l31) * 4u;
     }
   }
 
@@ -367,11 +393,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
       for (int i = 0; i < B_INSTR; ++i) lds_dma16(srdW, stage + A_BYTES + (i * NW + wave) * 1024, voffB[i], sB_set[set]);
     };
 
-    f32x16 acc[TI][TJ];
+    f32x16 acc[TI][KTJ];
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
-      for (int j = 0; j < TJ; ++j)
+      for (int j = 0; j < KTJ; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
@@ -424,18 +450,18 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
         if (it + NSTAGE - 1 < total) issue(std::integral_constant<int, (cur + NSTAGE - 1) % NSTAGE>{});
       }
       constexpr unsigned stage_off = (unsigned)(cur * STAGE_BYTES);
-      f32x4v fa[2][TI], fb[2][w_nk ? TJ : 1];
-      float fk[2][w_nk ? 1 : TJ][4];
+      f32x4v fa[2][TI], fb[2][w_nk ? KTJ : 1];
+      float fk[2][w_nk ? 1 : KTJ][4];
       auto read_step = [&](auto qc, auto setc) {
         constexpr int q = decltype(qc)::value, set = decltype(setc)::value;
 #pragma unroll
         for (int i = 0; i < TI; ++i) lds_frag_f4<0>(fa[set][i], lds_base + stage_off + aoff[i][q]);
         if constexpr (w_nk) {
 #pragma unroll
-          for (int j = 0; j < TJ; ++j) lds_frag_f4<0>(fb[set][j], lds_base + stage_off + boff[j][w_nk ? q : 0]);
+          for (int j = 0; j < KTJ; ++j) lds_frag_f4<0>(fb[set][j], lds_base + stage_off + boff[j][w_nk ? q : 0]);
         } else {
 #pragma unroll
-          for (int j = 0; j < TJ; ++j) {
+          for (int j = 0; j < KTJ; ++j) {
             lds_frag_f1<(8 * q + 0) * B_ROWB>(fk[set][j][0], lds_base + stage_off + boff[j][0]);
             lds_frag_f1<(8 * q + 1) * B_ROWB>(fk[set][j][1], lds_base + stage_off + boff[j][0]);
             lds_frag_f1<(8 * q + 2) * B_ROWB>(fk[set][j][2], lds_base + stage_off + boff[j][0]);
@@ -446,18 +472,18 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
       auto fence = [&](auto setc) {
         constexpr int set = decltype(setc)::value;
         if constexpr (w_nk) {
-          if constexpr (TI == 2 && TJ == 2) MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fa[set][1]), "+v"(fb[set][0]), "+v"(fb[set][1]) :: "memory");
+          if constexpr (TI == 2 && KTJ == 2) MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fa[set][1]), "+v"(fb[set][0]), "+v"(fb[set][1]) :: "memory");
           else if constexpr (TI == 2) MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fa[set][1]), "+v"(fb[set][0]) :: "memory");
-          else if constexpr (TJ == 2) MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fb[set][0]), "+v"(fb[set][1]) :: "memory");
+          else if constexpr (KTJ == 2) MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fb[set][0]), "+v"(fb[set][1]) :: "memory");
           else MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fb[set][0]) :: "memory");
         } else {
-          if constexpr (TI == 2 && TJ == 2)
+          if constexpr (TI == 2 && KTJ == 2)
             MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fa[set][1]), "+v"(fk[set][0][0]), "+v"(fk[set][0][1]), "+v"(fk[set][0][2]),
                              "+v"(fk[set][0][3]), "+v"(fk[set][1][0]), "+v"(fk[set][1][1]), "+v"(fk[set][1][2]), "+v"(fk[set][1][3]) :: "memory");
           else if constexpr (TI == 2)
             MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fa[set][1]), "+v"(fk[set][0][0]), "+v"(fk[set][0][1]), "+v"(fk[set][0][2]),
                              "+v"(fk[set][0][3]) :: "memory");
-          else if constexpr (TJ == 2)
+          else if constexpr (KTJ == 2)
             MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0]), "+v"(fk[set][0][0]), "+v"(fk[set][0][1]), "+v"(fk[set][0][2]),
                              "+v"(fk[set][0][3]), "+v"(fk[set][1][0]), "+v"(fk[set][1][1]), "+v"(fk[set][1][2]), "+v"(fk[set][1][3]) :: "memory");
           else
@@ -471,7 +497,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int j = 0; j < TJ; ++j) {
+          for (int j = 0; j < KTJ; ++j) {
             const float b = w_nk ? fb[set][w_nk ? j : 0][e] : fk[set][w_nk ? 0 : j][e];
 #pragma unroll
             for (int i = 0; i < TI; ++i)
@@ -515,6 +541,47 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gather_gemm_f32_glds_kernel
     }
     __syncthreads();   // every wave is done with the operand buffers: the epilogue's staging patches overlay them
 
+    if constexpr (WGK == 2) {
+      // ---- K-partitioned waves: one reduction across the two k halves per M tile -----------------------------------
+      // Wave (wm, kh) keeps tile column kh of the block -- its acc[.][0], see boff -- and gets the partner's sums for it; the other
+      // column, acc[.][1], goes to the partner (wave ^ 1) through a private TI x 4 KB slot at the start of the operand stages.
+      // Those are dead: the last chunk's top waited for vmcnt(0) in every wave (no LDS-DMA of this tile is in flight), and the
+      // barrier above says both k halves have read their fragments of it.  The next tile's prologue DMA is issued behind the
+      // barrier that ends the epilogue.  The accesses are assembly, like every LDS access of the main loop; the wave counts
+      // lgkmcnt for them itself.  Only the order of fp32 additions differs from one wave walking all of k: two chains over half
+      // the k each, then one add.
+      constexpr int X_BYTES = TI * 4096;
+      static_assert(NW * X_BYTES <= NSTAGE * STAGE_BYTES, "the exchange slots overlay the operand stages");
+      const unsigned x_own = lds_base + (unsigned)(wave * X_BYTES) + (unsigned)lane * 16u;
+      const unsigned x_partner = lds_base + (unsigned)((wave ^ 1) * X_BYTES) + (unsigned)lane * 16u;
+      // (plain loops: a lambda that is not inlined here would put the accumulators into scratch memory)
+#pragma unroll
+      for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          lds_store_b128(x_own + (unsigned)((i * 4 + g) * 1024),
+                         u32x4{__float_as_uint(acc[i][1][4 * g]), __float_as_uint(acc[i][1][4 * g + 1]), __float_as_uint(acc[i][1][4 * g + 2]),
+                               __float_as_uint(acc[i][1][4 * g + 3])});
+      MOPOE_DEVICE_ASM("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        u32x4 t0, t1, t2, t3;
+        lds_load_x4(t0, t1, t2, t3, x_partner + (unsigned)(i * 4096));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          acc[i][0][e] += __uint_as_float(t0[e]);
+          acc[i][0][4 + e] += __uint_as_float(t1[e]);
+          acc[i][0][8 + e] += __uint_as_float(t2[e]);
+          acc[i][0][12 + e] += __uint_as_float(t3[e]);
+        }
+      }
+      __syncthreads();   // every wave has read its partner's slot: the staging patches overlay the slots too
+    }
+
+    // (epilogue names from here on: acc[i][j], j < TJ)
 #include "gemm_epilogue_rows.inc"
   }
 

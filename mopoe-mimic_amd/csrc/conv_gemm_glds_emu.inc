@@ -1,6 +1,7 @@
 // The main loop of gather_gemm_f32_glds_kernel<..., EMU = 1>: fp32 products on the bf16 matrix pipe (split3, conv_gemm_glds.inc).
 // Textually included in the kernel's tile loop, in place of the chunk() loop of the fp32-MFMA form: same stages, same DMA
-// issue / counted vmcnt wait / barrier at the top of a chunk, same accumulators and epilogue.
+// issue / counted vmcnt wait / barrier at the top of a chunk, same accumulators and epilogue.  (KTJ = tile columns of the wave in
+// the main loop: TJ of the epilogue unless the waves are K-partitioned, WGK = 2 -- then each wave works on ONE pair of the chunk.)
 //
 // A chunk of 32 k is two PAIRS of super-steps (16 k each = one bf16 MFMA step): read, split and multiply a pair at a time, the
 // second pair's reads in flight behind the first pair's MFMAs.  What overlaps the VALU instructions of one wave's split with
@@ -12,11 +13,11 @@
 // MFMAs per pair -- stays VALU-bound with nobody to fill the matrix pipe meanwhile).
 {
   static_assert(!xform, "EMU: plain operand forms");
-  constexpr int NM = 6 * TI * TJ;                          // MFMAs of a pair
-  constexpr int NP = 4 * (TI + TJ);                        // split3_pair pieces of a pair (four per fragment)
-  f32x4v ea[2][TI], eb[2][w_nk ? TJ : 1];
-  float ek[2][w_nk ? 1 : TJ][4];
-  Split3 sa[2][TI], sb[2][TJ];                         // one split set per pair
+  constexpr int NM = 6 * TI * KTJ;                         // MFMAs of a pair
+  constexpr int NP = 4 * (TI + KTJ);                       // split3_pair pieces of a pair (four per fragment)
+  f32x4v ea[2][TI], eb[2][w_nk ? KTJ : 1];
+  float ek[2][w_nk ? 1 : KTJ][4];
+  Split3 sa[2 / WGK][TI], sb[2 / WGK][KTJ];                // one split set per pair the wave works on
 
   auto top = [&](int it, auto curc) {
     constexpr int cur = decltype(curc)::value;
@@ -29,7 +30,8 @@
     __builtin_amdgcn_sched_barrier(0);
     if (it + NSTAGE - 1 < total) issue(std::integral_constant<int, (cur + NSTAGE - 1) % NSTAGE>{});
   };
-  // the lane's eight k of pair p (super-steps 2 p and 2 p + 1) of the stage in buffer cur
+  // the lane's eight k of pair p (super-steps 2 p and 2 p + 1) of the stage in buffer cur (K-partitioned: p = 0 is the wave's
+  // own pair, the offsets hold its place in the chunk)
   auto reads = [&](auto curc, auto pc) {
     constexpr unsigned stage_off = (unsigned)(decltype(curc)::value * STAGE_BYTES);
     constexpr int p = decltype(pc)::value;
@@ -39,10 +41,10 @@
       for (int i = 0; i < TI; ++i) lds_frag_f4<0>(ea[s][i], lds_base + stage_off + aoff[i][q]);
       if constexpr (w_nk) {
 #pragma unroll
-        for (int j = 0; j < TJ; ++j) lds_frag_f4<0>(eb[s][w_nk ? j : 0], lds_base + stage_off + boff[j][w_nk ? q : 0]);
+        for (int j = 0; j < KTJ; ++j) lds_frag_f4<0>(eb[s][w_nk ? j : 0], lds_base + stage_off + boff[j][w_nk ? q : 0]);
       } else {
 #pragma unroll
-        for (int j = 0; j < TJ; ++j) {
+        for (int j = 0; j < KTJ; ++j) {
           lds_frag_f1<(8 * q + 0) * B_ROWB>(ek[s][w_nk ? 0 : j][0], lds_base + stage_off + boff[j][0]);
           lds_frag_f1<(8 * q + 1) * B_ROWB>(ek[s][w_nk ? 0 : j][1], lds_base + stage_off + boff[j][0]);
           lds_frag_f1<(8 * q + 2) * B_ROWB>(ek[s][w_nk ? 0 : j][2], lds_base + stage_off + boff[j][0]);
@@ -59,10 +61,10 @@
       for (int i = 0; i < TI; ++i) pin_reg(ea[s][i]);
       if constexpr (w_nk) {
 #pragma unroll
-        for (int j = 0; j < TJ; ++j) pin_reg(eb[s][w_nk ? j : 0]);
+        for (int j = 0; j < KTJ; ++j) pin_reg(eb[s][w_nk ? j : 0]);
       } else {
 #pragma unroll
-        for (int j = 0; j < TJ; ++j)
+        for (int j = 0; j < KTJ; ++j)
 #pragma unroll
           for (int e = 0; e < 4; ++e) pin_reg(ek[s][w_nk ? 0 : j][e]);
       }
@@ -87,10 +89,11 @@
   // MFMA t of split set d, term-major (consecutive MFMAs go to different accumulators)
   auto mfma_t = [&](auto tc, auto dc) {
     constexpr int t = decltype(tc)::value, d = decltype(dc)::value;
-    constexpr int term = t / (TI * TJ), tile = t % (TI * TJ), i = tile % TI, j = tile / TI;
+    constexpr int term = t / (TI * KTJ), tile = t % (TI * KTJ), i = tile % TI, j = tile / TI;
     mfma_split_term<term>(acc[i][j], sa[d][i], sb[d][j]);
   };
   using E0 = std::integral_constant<int, 0>; using E1 = std::integral_constant<int, 1>;
+  using S1 = std::integral_constant<int, 2 / WGK - 1>;     // split set of the second pair
   auto all_pieces = [&](auto dc) { static_for<NP>([&](auto uc) { piece(uc, dc); }); };
   auto all_mfma = [&](auto dc) { static_for<NM>([&](auto tc) { mfma_t(tc, dc); }); };
   auto chunk2 = [&](int it, auto curc) {
@@ -103,18 +106,33 @@
     all_mfma(E0{});
     __builtin_amdgcn_sched_barrier(0);
     fence_e();
-    all_pieces(E1{});
+    all_pieces(S1{});
     __builtin_amdgcn_sched_barrier(0);
-    all_mfma(E1{});
+    all_mfma(S1{});
     __builtin_amdgcn_sched_barrier(0);
+  };
+  // K-partitioned: the wave's one pair of the chunk.  Nothing of its own to put behind the MFMAs -- the next reads need the next
+  // barrier -- so what covers the reads and the split is the other waves of the SIMD, as in the first pair above
+  auto chunk1 = [&](int it, auto curc) {
+    top(it, curc);
+    reads(curc, E0{});
+    fence_e();
+    all_pieces(E0{});
+    __builtin_amdgcn_sched_barrier(0);
+    all_mfma(E0{});
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto chunk_e = [&](int it, auto curc) {
+    if constexpr (WGK == 2) chunk1(it, curc);
+    else chunk2(it, curc);
   };
   int it = 0;
   while (it < total) {
-    chunk2(it, std::integral_constant<int, 0>{});
+    chunk_e(it, std::integral_constant<int, 0>{});
     if (++it >= total) break;
-    chunk2(it, std::integral_constant<int, 1>{});
+    chunk_e(it, std::integral_constant<int, 1>{});
     if (++it >= total) break;
-    if constexpr (NSTAGE >= 3) { chunk2(it, std::integral_constant<int, 2 % NSTAGE>{}); if (++it >= total) break; }
-    if constexpr (NSTAGE >= 4) { chunk2(it, std::integral_constant<int, 3 % NSTAGE>{}); ++it; }
+    if constexpr (NSTAGE >= 3) { chunk_e(it, std::integral_constant<int, 2 % NSTAGE>{}); if (++it >= total) break; }
+    if constexpr (NSTAGE >= 4) { chunk_e(it, std::integral_constant<int, 3 % NSTAGE>{}); ++it; }
   }
 }

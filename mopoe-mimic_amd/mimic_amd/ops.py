@@ -1334,7 +1334,7 @@ def _prof_kind_names():
     names[140], names[141] = "wgrad_parity_f32_kernel<64, true>", "wgrad_parity_f32_kernel<64, false>"
     names[142], names[143] = "wgrad_parity_f32_kernel<128, true>", "wgrad_parity_f32_kernel<128, false>"
     names[138], names[139] = "wgrad_gemm_f32_glds_kernel<128, false, 2, 1>", "wgrad_gemm_f32_glds_kernel<64, false, 4, 1>"
-    for i, tt in enumerate(("128, 128, 2, 2, {}, 2, 1", "128, 64, 2, 2, {}, 3, 1", "64, 64, 2, 2, {}, 4, 1", "256, 128, 4, 2, {}, 3, 1")):
+    for i, tt in enumerate(("128, 128, 2, 2, {}, 2, 1, 1", "128, 64, 2, 1, {}, 3, 2, 1", "64, 64, 2, 1, {}, 4, 2, 1", "256, 128, 4, 2, {}, 3, 1, 1")):
         for k, spec in enumerate((1, 3)):
             names[130 + 2 * i + k] = f"gather_gemm_f32_glds_kernel<{tt.format(spec)}>"
     names[127], names[128], names[129] = "pw_front_fwd_f32_kernel<false>", "pw_front_fwd_f32_kernel<true>", "pw_front_bwd_f32_kernel"
@@ -1345,7 +1345,7 @@ def _prof_kind_names():
     for i, (tt, st) in enumerate((("128", (2, 2)), ("64", (4, 2)))):
         for xf in (0, 1):
             names[116 + 2 * i + xf] = f"wgrad_gemm_f32_glds_kernel<{tt}, {'true' if xf else 'false'}, {st[xf]}, 0>"
-    for i, tt in enumerate(("128, 128, 2, 2, {}, 2, 0", "128, 64, 2, 2, {}, 3, 0", "64, 64, 2, 2, {}, 4, 0", "256, 128, 4, 2, {}, 2, 0")):
+    for i, tt in enumerate(("128, 128, 2, 2, {}, 2, 1, 0", "128, 64, 2, 2, {}, 3, 1, 0", "64, 64, 2, 2, {}, 4, 1, 0", "256, 128, 4, 2, {}, 2, 1, 0")):
         for spec in (1, 2, 3):
             names[104 + 3 * i + spec - 1] = f"gather_gemm_f32_glds_kernel<{tt.format(spec)}>"
     for i, tt in enumerate(("128", "64")):
