@@ -94,24 +94,9 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- profiling (api.hip) ----------------------------------------------------------------------------
-// one kind per kernel instantiation, so that the names bench.py reports are the names rocprofv3 prints:
-//   gather, vector path:  tile * 4 + spec            (tile 0..7, spec 0..3)        kinds  0..31
-//   gather, scalar path:  32 + {0: 128x128, 1: 256x64, 2: 64x64}                   kinds 32..34
-//   wgrad,  vector path:  36 + (128x128 ? 0 : 3) + spec   (spec 0..2)              kinds 36..41
-//   wgrad,  scalar path:  42 + (128x128 ? 0 : 1)                                   kinds 42..43
-//   direct (LDS-free) gather: 44 + (tile - 8) * 4 + spec                           kinds 44..59
-//   bf16 gather:          60 + tile * 3 + (spec - 1)     (tile 0..4, spec 1..3)    kinds 60..74
-//   bf16 wgrad:           75 + (128x128 ? 0 : 2) + (BN+ReLU on x ? 1 : 0)          kinds 75..78
-//   bf16 gather, LDS-DMA: 80 + (tile - 5) * 2 + (input gradient ? 1 : 0)           kinds 80..93
-//   the same with BN + ReLU on the operand (tiles 5, 7, 9): 94 + (tile - 5) / 2     kinds 94..96
-//   bf16 wgrad, LDS-DMA:  100 + (128x128 ? 0 : 2) + (BN+ReLU on x ? 1 : 0)         kinds 100..103
-//   fp32 gather, LDS-DMA: 104 + (tile - 12) * 3 + (spec - 1)                       kinds 104..115
-//   fp32 wgrad, LDS-DMA:  116 + (128x128 ? 0 : 2) + (BN+ReLU on x ? 1 : 0)         kinds 116..119
-//   fp32 gather, LDS-DMA, products on the bf16 pipe: 130 + (tile - 16) * 2 + (input gradient ? 1 : 0)   kinds 130..137
-//   fp32 wgrad,  LDS-DMA, products on the bf16 pipe: 138 + (128x128 ? 0 : 1)       kinds 138..139
-//   fp32 wgrad, four taps per block, products on the bf16 pipe (tile 9)            kinds 140..143: (S tile 128 ? 2 : 0) + (transposed conv ? 1 : 0)
-enum { PROF_GATHER_VEC = 0, PROF_GATHER_SCALAR = 32, PROF_WGRAD_VEC = 36, PROF_WGRAD_SCALAR = 42, PROF_DIRECT = 44,
-       PROF_BF16_GATHER = 60, PROF_BF16_WGRAD = 75, PROF_BF16_GLDS = 80, PROF_BF16_GLDS_X = 94, PROF_BF16_WGRAD_GLDS = 100, PROF_F32_GLDS = 104, PROF_F32_WGRAD_GLDS = 116, PROF_BF16_WGRAD_GLDS_MERGE = 120, PROF_BF16_WGRAD_PARITY = 122, PROF_PW_FRONT = 124, PROF_F32_GLDS_EMU = 130, PROF_F32_WGRAD_GLDS_EMU = 138, PROF_F32_WGRAD_PARITY = 140, PROF_NKINDS = MOPOE_PROF_KINDS };
+// one kind per kernel instantiation, so that the names bench.py reports are the names rocprofv3 prints.  The conv families'
+// kinds stand beside their tile tables (conv_launch.hpp); 124..129 are the block fronts of pointwise.hip
+enum { PROF_PW_FRONT = 124, PROF_NKINDS = MOPOE_PROF_KINDS };
 struct ProfScope {
   hipStream_t stream;
   int slot;

@@ -21,36 +21,13 @@
 // (weights, wgrad's pixel slots), out-of-range rows read zeros through the hardware range check (voffset 2^31),
 // LDS addresses are base + immediate (loop unrolled by two), and the mode flags are template specialisations.
 // The tile and the split of the reduction are launch-plan arguments (mopoe_conv_plan): the host mirror measures
-// the candidates per layer; the heuristics in launch_gather / mopoe_conv_wgrad are only the fallback.
+// the candidates per layer; the heuristics in conv_launch.hpp (decide_gather / decide_wgrad) are only the fallback.
 #include "gemm_common.hpp"
 
 namespace mopoe {
 
-constexpr int BK = 16;            // K-chunk of the wgrad kernel and of the 64x64 gather tile
-#ifndef TILE_N64_REMAINDER
-#define TILE_N64_REMAINDER 64
-#endif
-#ifndef SPLIT_BLOCKS
-#define SPLIT_BLOCKS 256   // grids below this many blocks split the tap x channel reduction
-#endif
-#ifndef SPLIT_TARGET
-#define SPLIT_TARGET 512   // ... until about this many blocks are in flight
-#endif
-#ifndef GEMM_8WAVES
-#define GEMM_8WAVES 1          // 512-thread blocks (8 waves, 64x32 per wave): 4 waves per SIMD hide the load/store phases
-#endif
-#ifndef PERSIST_BLOCKS
-// upper bound on blocks of one launch (each block walks the M tiles it owns).  512 = exactly the 2 x 8-wave blocks a CU
-// holds: fastest for a kernel that is alone on the chip, but inside the replayed step such a kernel keeps every CU for its
-// whole duration and the other branches' small kernels wait.  With 2048 blocks retire 4x as often: C2 step +1...2 %
-// (5250-5260 -> 5305-5370 samples/s; 4096: 5339, 16384: 5324); the bf16 family measured the other way and stays at 512.
-#define PERSIST_BLOCKS 2048
-#endif
 #ifndef GEMM_MIN_WAVES
 #define GEMM_MIN_WAVES 3
-#endif
-#ifndef GEMM_BK_BIG
-#define GEMM_BK_BIG 16           // K-chunk of the 128x128 / 256x64 gather tiles
 #endif
 #ifndef GEMM_LDS_PAD
 #define GEMM_LDS_PAD 4
@@ -1081,214 +1058,83 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const GemmArgs a) 
 #include "conv_gemm_glds_parity.inc"
 
 
+// ---- host-side launchers ---------------------------------------------------------------------------------------------------
+// What is launched is decided in conv_launch.hpp (decide_gather / decide_wgrad); here the argument struct is filled from the
+// decision and the tile's kernel is named: one launch_<kernel> per kernel of the tile tables, instantiated by the table's rows.
+#define MOPOE_GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(THREADS), 0, stream, a)
+// specialised main loops (spec != 0); the run-time form walks K 16 deep
+template <int BM, int BN, int WM, int WN, int WK, int GBK, int ST, bool XF>
+static void launch_LDS(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+  constexpr int THREADS = 64 * WM * WN;
+  if (d.spec == 1) MOPOE_GO(gather_gemm_kernel<BM, BN, WM, WN, GBK, true, 1>);
+  else if (d.spec == 2) MOPOE_GO(gather_gemm_kernel<BM, BN, WM, WN, GBK, true, 2>);
+  else if (d.spec == 3) MOPOE_GO(gather_gemm_kernel<BM, BN, WM, WN, GBK, true, 3>);
+  else MOPOE_GO(gather_gemm_kernel<BM, BN, WM, WN, 16, true, 0>);
+}
+// ... and the scalar path: the same block tile on four waves
+template <int BM, int BN, int WM, int WN, int WK, int GBK, int ST, bool XF>
+static void launch_LDS_S(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+  constexpr int THREADS = 256;
+  if (d.vec) launch_LDS<BM, BN, WM, WN, WK, GBK, ST, XF>(d, grid, stream, a);
+  else MOPOE_GO(gather_gemm_kernel<BM, BN, WM, 4 / WM, GBK, false>);
+}
+template <int BM, int BN, int WM, int WN, int WK, int GBK, int ST, bool XF>
+static void launch_DIRECT(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+  constexpr int THREADS = 64 * WM * WN, TI = BM / (32 * WM), TJ = BN / (32 * WN);
+  if (d.spec == 1) MOPOE_GO(direct_gemm_kernel<WM, WN, TI, TJ, 1>);
+  else if (d.spec == 2) MOPOE_GO(direct_gemm_kernel<WM, WN, TI, TJ, 2>);
+  else MOPOE_GO(direct_gemm_kernel<WM, WN, TI, TJ, 3>);
+}
+template <int BM, int BN, int WM, int WN, int WK, int GBK, int ST, bool XF>
+static void launch_GLDS(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+  constexpr int THREADS = 64 * WM * WN;
+  if (d.spec == 1) MOPOE_GO(gather_gemm_f32_glds_kernel<BM, BN, WM, WN, 1, ST>);
+  else if (d.spec == 3) MOPOE_GO(gather_gemm_f32_glds_kernel<BM, BN, WM, WN, 3, ST>);
+  else if constexpr (XF) MOPOE_GO(gather_gemm_f32_glds_kernel<BM, BN, WM, WN, 2, ST>);
+}
+template <int BM, int BN, int WM, int WN, int WK, int GBK, int ST, bool XF>
+static void launch_EMU(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgs& a) {
+  constexpr int THREADS = 64 * WM * WN * WK;
+  if (d.spec == 1) MOPOE_GO(gather_gemm_f32_glds_kernel<BM, BN, WM, WN, 1, ST, WK, 1>);
+  else MOPOE_GO(gather_gemm_f32_glds_kernel<BM, BN, WM, WN, 3, ST, WK, 1>);
+}
+
 // dest_on_small: 1 -> form 0 (Y on the small grid), 0 -> form 1 (Y on the big grid)
 static int launch_gather(const float* X, const float* W, const float* bias, float* Y, const mopoe_conv_geom* g,
                          int dest_on_small, int Ck, int Cn, int w_nk, const mopoe_bn_ref* bn_in,
                          const mopoe_mask_ref* mask, double* out_stats, const mopoe_bn_ref* relu_bn,
                          const float* xin, double* bwd_sums, const mopoe_conv_plan* plan, void* ws, size_t ws_bytes,
                          hipStream_t stream, const mopoe_mix_ref* mix = nullptr) {
-  // the head of the workspace holds the arrival counters of in-kernel split reductions (kept zero by the kernels)
-  int* counters = nullptr;
-  if (ws && ws_bytes > WS_COUNTER_BYTES) { counters = (int*)ws; ws = (char*)ws + WS_COUNTER_BYTES; ws_bytes -= WS_COUNTER_BYTES; }
-  else { ws = nullptr; ws_bytes = 0; }
+  const mopoe_bn_ref none = {};
+  const mopoe_mask_ref nomask = {nullptr, 0, 1};
   GemmArgs a;
-  a.X = X; a.W = W; a.Y = Y; a.bias = bias;
-  a.N = g->N; a.Ck = Ck; a.Cn = Cn; a.Cin_w = g->Cin; a.Cout_w = g->Cout;
-  a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
-  a.w_nk = w_nk;
-  int nphase;
-  if (dest_on_small) {
-    a.form = 0; a.Hx = g->Hb; a.Wx = g->Wb; a.Hy = g->Hs; a.Wy = g->Ws; a.Hq = g->Hs; a.Wq = g->Ws; nphase = 1;
-  } else {
-    a.form = 1; a.Hx = g->Hs; a.Wx = g->Ws; a.Hy = g->Hb; a.Wy = g->Wb; a.Hq = g->Hb / g->sh; a.Wq = g->Wb / g->sw;
-    nphase = g->sh * g->sw;
-  }
-  a.rows_per_phase = (long)g->N * a.Hq * a.Wq;
-  a.rows_total = (long)g->N * a.Hy * a.Wy;
-  a.vecA = (Ck % 4 == 0) && aligned16(X);
-  a.vecB = (g->Cout % 4 == 0) && aligned16(W);
-  const size_t xb = (size_t)g->N * a.Hx * a.Wx * Ck * sizeof(float);
-  const size_t wb = (size_t)g->kh * g->kw * g->Cin * g->Cout * sizeof(float);
-  // branch-free buffer loads need 16-byte alignment, channel counts that are multiples of 4 and < 2 GiB operands
-  // (the vector path's row-major epilogue moves the result, xin and the mask in float4 pieces: Cn % 4 == 0, aligned rows)
-  const bool vec = a.vecA && a.vecB && xb < (1ull << 31) && wb < (1ull << 31) && Cn % 4 == 0 && aligned16(Y) &&
-                   (!xin || aligned16(xin)) && (!mask || mask->kind == 0 || aligned16(mask->mask));
-  a.x_bytes = (unsigned)std::min<size_t>(xb, 0x7fffffffu);
-  a.w_bytes = (unsigned)std::min<size_t>(wb, 0x7fffffffu);
-  mopoe_bn_ref none = {};
-  mopoe_mask_ref nomask = {nullptr, 0, 1};
   a.bn_in = bn_in ? *bn_in : none;
   a.mask = mask ? *mask : nomask;
-  a.out_stats = out_stats;
-  a.relu_bn = relu_bn ? *relu_bn : none;
-  a.xin = xin; a.bwd_sums = bwd_sums;
-  a.mix = 0; a.mix_a = a.mix_b = 0.f;
-  static const bool xcd_remap_g = !getenv("MOPOE_NO_XCD_REMAP");   // (A/B switch)
-  a.xcd_remap = xcd_remap_g ? 1 : 0;
-  if (mix) {   // residual mix in the epilogue: the shortcut's BN rides in relu_bn, its tensor in xin (vector path only)
-    if (!mix->s || mix->bn.mode == 0 || relu_bn || xin) { set_error("conv_fwd_mix: needs s and its BatchNorm"); return MOPOE_ERR_ARG; }
-    if (!vec || !aligned16(mix->s)) { set_error("conv_fwd_mix: channel counts must be multiples of 4 and tensors 16-byte aligned"); return MOPOE_ERR_ARG; }
-    a.mix = 1; a.mix_a = mix->a; a.mix_b = mix->b;
-    a.relu_bn = mix->bn; a.xin = (const float*)mix->s;
-  }
-  a.nsplit = 1; a.partial = nullptr; a.counters = nullptr;
+  // residual mix in the epilogue: the shortcut's BN rides in relu_bn, its tensor in xin
+  a.relu_bn = mix ? mix->bn : (relu_bn ? *relu_bn : none);
+  a.xin = mix ? (const float*)mix->s : xin;
+  GatherFacts f = {dest_on_small, Ck, Cn, w_nk, a.bn_in.mode, a.bn_in.C, a.relu_bn.mode, a.relu_bn.C, a.xin != nullptr,
+                   a.mask.kind, a.mask.mask != nullptr, a.mask.rows_per_sample, mix != nullptr, mix && mix->s && mix->bn.mode != 0, true,
+                   aligned16(X), aligned16(W), aligned16(Y), aligned16(xin), aligned16(a.mask.mask), mix && aligned16(mix->s),
+                   plan ? plan->tile : -1, plan ? plan->split : 0, ws != nullptr, ws_bytes, xcd_remap_enabled(), true};
+  GatherDecision d;
+  char msg[512];
+  if (int rc = decide_gather(CONV_F32, g, f, d, msg, sizeof msg)) { set_error("%s", msg); return rc; }
+  fill_gather_args(a, d, g, X, W, bias, Y, Ck, Cn, out_stats, bwd_sums, mix, ws);
+  a.w_nk = w_nk; a.vecA = d.vecA; a.vecB = d.vecB;
   static const bool dbg_nostats = getenv("MOPOE_DEBUG_NOSTATS") != nullptr;  // timing experiments only
   if (dbg_nostats) { a.out_stats = nullptr; a.bwd_sums = nullptr; }
-  if (a.bn_in.mode != 0 && (a.bn_in.C != Ck || Ck > MAX_BN_C)) { set_error("bn_in channel mismatch (%d vs %d)", a.bn_in.C, Ck); return MOPOE_ERR_ARG; }
-  if (a.relu_bn.mode != 0 && (a.relu_bn.C != Cn || !a.xin)) { set_error("relu_bn needs xin and C == %d", Cn); return MOPOE_ERR_ARG; }
-  if (a.mask.kind != 0 && !a.mask.mask) { set_error("mask pointer missing"); return MOPOE_ERR_ARG; }
-  if (a.mask.kind == 1 && a.mask.rows_per_sample != a.Hy * a.Wy) { set_error("channel mask: rows_per_sample must be Hout*Wout"); return MOPOE_ERR_ARG; }
-  if (a.rows_total >= (1L << 31) || (long)g->N * a.Hx * a.Wx >= (1L << 31)) { set_error("conv: more than 2^31 rows"); return MOPOE_ERR_ARG; }
-
-  // ---- tile choice -------------------------------------------------------------------------------------------
-  // 0: 128x128 (2x2 waves)   1: 256x64 (4x1 waves; narrow outputs, many rows)   2: 64x64 (2x2 waves)
-  // Wide outputs always take the 128x128 tile (best operand reuse); when that leaves the chip under-filled the
-  // tap x channel reduction is split across blocks instead of shrinking the tile.
-  int cfg;
-  bool emu = false;
-  if (Cn > 64) cfg = (a.rows_per_phase > 64 || Cn >= 256) ? 0 : 2;
-  else cfg = a.rows_per_phase >= 256L * 64 ? 1 : 2;
-#ifdef TILE_N64_REMAINDER
-  // a 128-wide tile would be half empty for the last 64 columns (Cout = 192, 320): use 64-wide tiles instead
-  if (cfg == 0 && (Cn % 128) == 64 && a.rows_per_phase >= 256L * TILE_N64_REMAINDER) cfg = 1;
-#endif
-  if (plan && plan->tile >= 0) {
-    if (plan->tile > 19) { set_error("conv plan: tile %d (see mopoe_conv_plan in mopoe_hip.h: 0..19)", plan->tile); return MOPOE_ERR_ARG; }
-    cfg = plan->tile;
-    // 16..19 = tiles 12..15 with the fp32 products on the bf16 matrix pipe (conv_gemm_glds.inc, EMU); not with BN on load
-    if (cfg >= 16) {
-      if (a.bn_in.mode != 0) { set_error("conv plan: tile %d (split-bf16 products) has no BN-on-load form", cfg); return MOPOE_ERR_ARG; }
-      emu = true;
-      cfg -= 4;
-    }
-    // 12..15 = LDS-DMA family (conv_gemm_glds.inc): vector path, K channels a multiple of 32; with BN on load the tiles with
-    // two or four buffers (12, 14, 15).  A plan that asks for one where it does not apply is refused (the tuner never offers it).
-    if (cfg >= 12 && (!vec || Ck % 32 != 0 || (a.bn_in.mode != 0 && cfg == 13))) {
-      set_error("conv plan: tile %d (LDS-DMA family) needs the vector path, K channels %% 32 == 0 (Ck = %d) and, with BN on load, tile 12, 14 or 15", cfg, Ck);
-      return MOPOE_ERR_ARG;
-    }
-    if (cfg >= 3 && !vec) cfg = cfg == 3 ? 0 : 2;   // the extra tiles exist for the vector path only
-    if ((cfg == 5 || cfg == 6) && Ck % 32 != 0) cfg -= 3;   // 5, 6 = tiles 2, 4 with a 32-deep K chunk
-    if (cfg >= 8 && cfg < 12 && (!vec || Ck % 8 != 0 || a.mix)) cfg = (cfg == 8) ? 0 : (cfg == 9 ? 1 : (cfg == 10 ? 2 : 4));   // 8..11 = LDS-free kernels (no residual mix)
-  }
-  static const int TILE_BM[16] = {128, 256, 64, 256, 128, 64, 128, 128, 128, 256, 64, 128, 128, 128, 64, 256};
-  static const int TILE_BN[16] = {128, 64, 64, 128, 64, 64, 64, 128, 128, 64, 64, 64, 128, 64, 64, 128};
-  const int bm = TILE_BM[cfg], bn = TILE_BN[cfg];
-  const long nMt = ceil_div(a.rows_per_phase, bm);
-  const int nNt = ceil_div(Cn, bn);
-  // ---- split-K for grids that cannot fill the chip --------------------------------------------------------------
-  const int gbk = (cfg == 5 || cfg == 6 || cfg >= 12) ? 32 : (cfg >= 8 ? 8 : 16);
-  const int nkc = ceil_div(Ck, gbk);
-  const int iters = (dest_on_small ? g->kh * g->kw : std::max(1, (g->kh / g->sh) * (g->kw / g->sw))) * nkc;
-  const long blocks = nMt * nNt * nphase;
-  const size_t per = (size_t)a.rows_total * Cn * sizeof(float);
-  if (plan && plan->split > 0) {
-    long ns = std::min<long>(plan->split, iters);
-    if (ns >= 2 && (!ws || (size_t)ns * per > ws_bytes)) {
-      set_error("conv plan: split %ld needs %zu workspace bytes (have %zu)", ns, (size_t)ns * per, ws ? ws_bytes : (size_t)0);
-      return MOPOE_ERR_ARG;
-    }
-    if (ns >= 2) { a.nsplit = (int)ns; a.partial = (float*)ws; }
-  } else if (ws && blocks < SPLIT_BLOCKS && iters * gbk >= 256) {
-    long ns = std::min<long>((SPLIT_TARGET + blocks - 1) / blocks, (long)iters * gbk / 128);
-    if ((size_t)ns * per > ws_bytes) ns = (long)(ws_bytes / per);
-    if (ns >= 2) { a.nsplit = (int)ns; a.partial = (float*)ws; }
-  }
-  // vector path, LDS kernels: the reduction finishes in the tile's last-arriving block (gemm_epilogue_rows.inc); the
-  // scalar path and the LDS-free kernels park raw slabs for splitk_epilogue_kernel
-  const bool in_kernel_reduce = vec && (cfg < 8 || cfg >= 12);
-  if (a.partial && in_kernel_reduce) {
-    if (blocks > (long)(WS_COUNTER_BYTES / sizeof(int))) { set_error("conv: split reduction over %ld output tiles (at most %zu)", blocks, WS_COUNTER_BYTES / sizeof(int)); return MOPOE_ERR_ARG; }
-    a.counters = counters;
-  }
-  // ---- persistent M loop: at most ~1024 blocks in flight, column statistics leave a block once -------------------
-  const long persist = cfg >= 12 ? (cfg == 15 ? 256 : 512)       // LDS-DMA tiles: resident blocks by LDS footprint (1 or 2 per CU)
-                                 : (cfg >= 8 ? 4096 : ((cfg == 2 || cfg >= 4) ? PERSIST_BLOCKS * 3 / 2 : PERSIST_BLOCKS));   // 4-wave blocks: 3 per CU
-  long gx = std::min<long>(nMt, std::max<long>(1, persist / ((long)nNt * nphase * a.nsplit)));
-  // algorithmic flops: every (output pixel, tap that exists) pair
-  double taps_eff = dest_on_small ? (double)g->kh * g->kw : (double)g->kh * g->kw / ((double)g->sh * g->sw);
-  const double flops = 2.0 * (double)g->N * a.Hy * a.Wy * (double)Cn * (double)Ck * taps_eff;
-  {
-    const int spec = (vec && Ck % gbk == 0) ? (w_nk ? 3 : (a.bn_in.mode != 0 ? 2 : 1)) : 0;
-    // algorithmic bytes: one read of the gathered activation + one write of the result
-    const double abytes = ((double)g->N * a.Hx * a.Wx * Ck + (double)a.rows_total * Cn) * sizeof(float);
-    ProfScope prof(stream, flops, emu ? PROF_F32_GLDS_EMU + (cfg - 12) * 2 + (spec == 3 ? 1 : 0)
-                                      : cfg >= 12 ? PROF_F32_GLDS + (cfg - 12) * 3 + (spec - 1)
-                                            : (cfg >= 8 ? PROF_DIRECT + (cfg - 8) * 4 + spec
-                                                        : (vec ? PROF_GATHER_VEC + cfg * 4 + spec : PROF_GATHER_SCALAR + cfg)), abytes);
-    dim3 grid((unsigned)gx, nNt, nphase * a.nsplit);
-    // specialised main loops (spec != 0): vector path with Ck a multiple of the K chunk (every layer of the four
-    // networks except the image-side edge layers, which do not come here, and the vocabulary projection's input gradient)
-#define MOPOE_LAUNCH_TILE(BM_, BN_, WM_, WN_, BK_, THREADS_)                                                                    \
-  do {                                                                                                                          \
-    if (spec == 1) hipLaunchKernelGGL((gather_gemm_kernel<BM_, BN_, WM_, WN_, BK_, true, 1>), grid, dim3(THREADS_), 0, stream, a);      \
-    else if (spec == 2) hipLaunchKernelGGL((gather_gemm_kernel<BM_, BN_, WM_, WN_, BK_, true, 2>), grid, dim3(THREADS_), 0, stream, a); \
-    else if (spec == 3) hipLaunchKernelGGL((gather_gemm_kernel<BM_, BN_, WM_, WN_, BK_, true, 3>), grid, dim3(THREADS_), 0, stream, a); \
-    else hipLaunchKernelGGL((gather_gemm_kernel<BM_, BN_, WM_, WN_, 16, true, 0>), grid, dim3(THREADS_), 0, stream, a);                \
-  } while (0)
-#define MOPOE_LAUNCH_DIRECT(WM_, WN_, TI_, TJ_)                                                                                   \
-  do {                                                                                                                          \
-    if (spec == 1) hipLaunchKernelGGL((direct_gemm_kernel<WM_, WN_, TI_, TJ_, 1>), grid, dim3(64 * WM_ * WN_), 0, stream, a);      \
-    else if (spec == 2) hipLaunchKernelGGL((direct_gemm_kernel<WM_, WN_, TI_, TJ_, 2>), grid, dim3(64 * WM_ * WN_), 0, stream, a); \
-    else hipLaunchKernelGGL((direct_gemm_kernel<WM_, WN_, TI_, TJ_, 3>), grid, dim3(64 * WM_ * WN_), 0, stream, a);                \
-  } while (0)
-#define MOPOE_LAUNCH_GLDS(BM_, BN_, WM_, WN_, ST_)                                                                                       \
-  do {                                                                                                                                \
-    if (spec == 1) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 1, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a); \
-    else hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 3, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a);          \
-  } while (0)
-#define MOPOE_LAUNCH_GLDS_EMU(BM_, BN_, WM_, WN_, ST_, WK_)                                                                              \
-  do {                                                                                                                                \
-    if (spec == 1) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 1, ST_, WK_, 1>), grid, dim3(64 * WM_ * WN_ * WK_), 0, stream, a); \
-    else hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<BM_, BN_, WM_, WN_, 3, ST_, WK_, 1>), grid, dim3(64 * WM_ * WN_ * WK_), 0, stream, a);          \
-  } while (0)
-    if (emu) {
-      // (tiles 17 and 18, whose 2 x 2 waves would each split fragments a neighbour splits too, partition K instead: 2 x 1 x 2
-      // waves, conv_gemm_glds.inc, WGK.  Same block, same stages, same epilogue layout)
-      if (cfg == 12) MOPOE_LAUNCH_GLDS_EMU(128, 128, 2, 2, 2, 1);
-      else if (cfg == 13) MOPOE_LAUNCH_GLDS_EMU(128, 64, 2, 1, 3, 2);
-      else if (cfg == 14) MOPOE_LAUNCH_GLDS_EMU(64, 64, 2, 1, 4, 2);
-      else MOPOE_LAUNCH_GLDS_EMU(256, 128, 4, 2, 3, 1);
-    }
-#undef MOPOE_LAUNCH_GLDS_EMU
-    else if (cfg >= 12) {
-      if (spec == 2) {
-        if (cfg == 12) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<128, 128, 2, 2, 2, 2>), grid, dim3(256), 0, stream, a);
-        else if (cfg == 14) hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<64, 64, 2, 2, 2, 4>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((gather_gemm_f32_glds_kernel<256, 128, 4, 2, 2, 2>), grid, dim3(512), 0, stream, a);
-      }
-      else if (cfg == 12) MOPOE_LAUNCH_GLDS(128, 128, 2, 2, 2);
-      else if (cfg == 13) MOPOE_LAUNCH_GLDS(128, 64, 2, 2, 3);
-      else if (cfg == 14) MOPOE_LAUNCH_GLDS(64, 64, 2, 2, 4);
-      else MOPOE_LAUNCH_GLDS(256, 128, 4, 2, 2);
-    }
-#undef MOPOE_LAUNCH_GLDS
-    else if (cfg == 8) MOPOE_LAUNCH_DIRECT(2, 2, 2, 2);
-    else if (cfg == 9) MOPOE_LAUNCH_DIRECT(4, 1, 2, 2);
-    else if (cfg == 10) MOPOE_LAUNCH_DIRECT(2, 2, 1, 1);
-    else if (cfg == 11) MOPOE_LAUNCH_DIRECT(2, 1, 2, 2);
-    else if (vec) {
-      if (cfg == 0) MOPOE_LAUNCH_TILE(128, 128, 2, 4, 16, 512);
-      else if (cfg == 1) MOPOE_LAUNCH_TILE(256, 64, 4, 2, 16, 512);
-      else if (cfg == 3) MOPOE_LAUNCH_TILE(256, 128, 4, 2, 16, 512);
-      else if (cfg == 4) MOPOE_LAUNCH_TILE(128, 64, 2, 2, 16, 256);
-      else if (cfg == 5) MOPOE_LAUNCH_TILE(64, 64, 2, 2, 32, 256);
-      else if (cfg == 6) MOPOE_LAUNCH_TILE(128, 64, 2, 2, 32, 256);
-      else if (cfg == 7) MOPOE_LAUNCH_TILE(128, 128, 2, 2, 16, 256);
-      else MOPOE_LAUNCH_TILE(64, 64, 2, 2, 16, 256);
-    } else {
-      if (cfg == 0) hipLaunchKernelGGL((gather_gemm_kernel<128, 128, 2, 2, GEMM_BK_BIG, false>), grid, dim3(256), 0, stream, a);
-      else if (cfg == 1) hipLaunchKernelGGL((gather_gemm_kernel<256, 64, 4, 1, 16, false>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((gather_gemm_kernel<64, 64, 2, 2, 16, false>), grid, dim3(256), 0, stream, a);
-    }
-#undef MOPOE_LAUNCH_TILE
-#undef MOPOE_LAUNCH_DIRECT
-    if (int rc = check_launch("gather_gemm")) return rc;
-    if (a.partial && !in_kernel_reduce) {
-      dim3 eg(ceil_div(Cn, 64), std::min<long>(ceil_div(a.rows_total, 4), EPI_MAX_BLOCKS_Y));
-      hipLaunchKernelGGL(splitk_epilogue_kernel, eg, dim3(256), 0, stream, a);
-      if (int rc = check_launch("splitk_epilogue")) return rc;
-    }
+  ProfScope prof(stream, d.flops, d.kind, d.bytes);
+  const dim3 grid((unsigned)d.gx, d.nNt, d.nphase * d.nsplit);
+#define MOPOE_CASE(K_, ID_, BM_, BN_, WM_, WN_, WK_, BK_, ST_, P_, X_, R_, KIND_) \
+  case ID_: launch_##K_<BM_, BN_, WM_, WN_, WK_, BK_, ST_, X_>(d, grid, stream, a); break;
+  switch (d.t->id) { MOPOE_F32_GATHER_TILES(MOPOE_CASE) }
+#undef MOPOE_CASE
+  if (int rc = check_launch("gather_gemm")) return rc;
+  if (d.reduce == REDUCE_EPILOGUE) {
+    dim3 eg(ceil_div(Cn, 64), std::min<long>(ceil_div(a.rows_total, 4), EPI_MAX_BLOCKS_Y));
+    hipLaunchKernelGGL(splitk_epilogue_kernel, eg, dim3(256), 0, stream, a);
+    if (int rc = check_launch("splitk_epilogue")) return rc;
   }
   return MOPOE_OK;
 }
@@ -1337,6 +1183,32 @@ extern "C" int mopoe_conv_dgrad(const float* dy, const float* wp, float* dx, con
                        nullptr, relu_bn, xin, bwd_sums, plan, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+template <int T, int ST, int STX>
+static void launch_W_REG(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgs& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (!d.vec) MOPOE_GO(wgrad_gemm_kernel<T, T, false>);
+  else if (d.spec == 1) MOPOE_GO(wgrad_gemm_kernel<T, T, true, 1>);
+  else if (d.spec == 2) MOPOE_GO(wgrad_gemm_kernel<T, T, true, 2>);
+  else MOPOE_GO(wgrad_gemm_kernel<T, T, true, 0>);
+}
+template <int T, int ST, int STX>
+static void launch_W_GLDS(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgs& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (d.bn_on_load) MOPOE_GO(wgrad_gemm_f32_glds_kernel<T, true, STX>);
+  else MOPOE_GO(wgrad_gemm_f32_glds_kernel<T, false, ST>);
+}
+template <int T, int ST, int STX>
+static void launch_W_EMU(const WgradDecision&, dim3 grid, hipStream_t stream, const WgradArgs& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  MOPOE_GO(wgrad_gemm_f32_glds_kernel<T, false, ST, 1>);
+}
+template <int T, int ST, int STX>
+static void launch_W_FOUR(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgs& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (d.x_is_big) MOPOE_GO(wgrad_parity_f32_kernel<T, true>);
+  else MOPOE_GO(wgrad_parity_f32_kernel<T, false>);
+}
+
 extern "C" int mopoe_conv_wgrad(const float* x, const float* dy, float* dwp, const mopoe_conv_geom* g,
                                 const mopoe_bn_ref* bn_in, int32_t dwp_is_zero, const mopoe_conv_plan* plan,
                                 void* stream_) {
@@ -1347,130 +1219,23 @@ extern "C" int mopoe_conv_wgrad(const float* x, const float* dy, float* dwp, con
     return edge_wgrad(dy, x, dwp, g, g->Cout, stream, dwp_is_zero != 0);
   if ((!bn_in || bn_in->mode == 0) && g->transposed && g->Cout == 1 && edge_supported(g, g->Cin, {x, dwp}))
     return edge_wgrad(x, dy, dwp, g, g->Cin, stream, dwp_is_zero != 0);
+  const mopoe_bn_ref none = {};
   WgradArgs a;
-  a.Xs = x; a.Dy = dy; a.dW = dwp;
-  a.N = g->N; a.Hs = g->Hs; a.Ws = g->Ws; a.Hb = g->Hb; a.Wb = g->Wb; a.Cin = g->Cin; a.Cout = g->Cout;
-  a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
-  a.x_is_big = g->transposed ? 0 : 1;
-  a.Ms = (long)g->N * g->Hs * g->Ws;
-  mopoe_bn_ref none = {};
   a.bn_in = bn_in ? *bn_in : none;
-  if (a.bn_in.mode != 0 && (a.bn_in.C != g->Cin || g->Cin > MAX_BN_C)) { set_error("wgrad bn_in channel mismatch"); return MOPOE_ERR_ARG; }
-  a.vecI = (g->Cin % 4 == 0) && aligned16(x);
-  a.vecJ = (g->Cout % 4 == 0) && aligned16(dy);
-  const size_t rows_x = (size_t)g->N * (g->transposed ? g->Hs * g->Ws : g->Hb * g->Wb);
-  const size_t rows_dy = (size_t)g->N * (g->transposed ? g->Hb * g->Wb : g->Hs * g->Ws);
-  const size_t xb = rows_x * g->Cin * sizeof(float), db = rows_dy * g->Cout * sizeof(float);
-  const bool vec = a.vecI && a.vecJ && xb < (1ull << 31) && db < (1ull << 31);
-  a.x_bytes = (unsigned)std::min<size_t>(xb, 0x7fffffffu);
-  a.dy_bytes = (unsigned)std::min<size_t>(db, 0x7fffffffu);
-  if (rows_x >= (1ull << 31) || rows_dy >= (1ull << 31)) { set_error("wgrad: more than 2^31 rows"); return MOPOE_ERR_ARG; }
-  // fast pixel addressing: chunks of BK = 16 pixels never straddle an image row (or cover whole rows of one image)
-  const int hw_s = g->Hs * g->Ws;
-  a.fast = (vec && ((g->Ws % BK == 0) || (BK % g->Ws == 0 && hw_s % BK == 0))) ? 1 : 0;
-  const int taps = g->kh * g->kw;
-  bool big = g->Cin > 64 && g->Cout > 64;
-  // plan tiles: 0 = 128x128, 2 = 64x64 (register-staged, 16 pixels per chunk); 5 = 128x128, 6 = 64x64 on LDS-DMA (32 pixels per
-  // stage: conv_gemm_glds.inc; vector path only)
-  // 9 = four taps (one parity class of a k4 s2 p1 kernel) per block, 64 x 64 channels, products on the bf16 matrix pipe
-  // (conv_gemm_glds_parity.inc: wgrad_parity_f32_kernel)
-  if (plan && (plan->tile == 9 || plan->tile == 10)) {
-    const bool ok = a.bn_in.mode == 0 && vec && g->kh == 4 && g->kw == 4 && g->sh == 2 && g->sw == 2 && g->ph == 1 && g->pw == 1 &&
-                    g->Hs % 8 == 0 && g->Ws % 8 == 0 && g->Hb == 2 * g->Hs && g->Wb == 2 * g->Ws;
-    if (!ok) {
-      set_error("wgrad plan: tiles 9 / 10 (four taps per block) need a plain operand, the vector path, k4 s2 p1 and a small grid of whole 8 x 8 tiles");
-      return MOPOE_ERR_ARG;
-    }
-    const int Cg = a.x_is_big ? g->Cin : g->Cout, Csm = a.x_is_big ? g->Cout : g->Cin;
-    const int cs = plan->tile == 10 ? 128 : 64;
-    if (cs == 128 && Csm % 128 != 0) { set_error("wgrad plan: tile 10 needs a multiple of 128 channels on the small-grid operand (%d)", Csm); return MOPOE_ERR_ARG; }
-    const long ntiles = (long)g->N * (g->Hs / 8) * (g->Ws / 8);
-    const long cblocks = (long)ceil_div(Cg, 64) * ceil_div(Csm, cs) * 4;
-    long split = plan->split > 0 ? plan->split : (256 + cblocks - 1) / cblocks;
-    if (split > ntiles) split = ntiles;
-    if (split < 1) split = 1;
-    a.chunk = (ntiles + split - 1) / split;             // (in 8 x 8 tiles)
-    split = (ntiles + a.chunk - 1) / a.chunk;
-    a.atomic = split > 1;
-    static const bool xcd_remap9 = !getenv("MOPOE_NO_XCD_REMAP");
-    a.xcd_remap = xcd_remap9 ? 1 : 0;
-    if (a.atomic && !dwp_is_zero) {
-      if (hipMemsetAsync(dwp, 0, (size_t)taps * g->Cin * g->Cout * sizeof(float), stream) != hipSuccess) { set_error("wgrad memset failed"); return MOPOE_ERR_LAUNCH; }
-    }
-    ProfScope prof(stream, 2.0 * (double)a.Ms * g->Cin * (double)g->Cout * taps, PROF_F32_WGRAD_PARITY + (cs == 128 ? 2 : 0) + (a.x_is_big ? 0 : 1), (double)xb + (double)db);
-    const dim3 grid((unsigned)(ceil_div(Cg, 64) * ceil_div(Csm, cs)), 4, (unsigned)split);
-    if (cs == 128 && a.x_is_big) hipLaunchKernelGGL((wgrad_parity_f32_kernel<128, true>), grid, dim3(256), 0, stream, a);
-    else if (cs == 128) hipLaunchKernelGGL((wgrad_parity_f32_kernel<128, false>), grid, dim3(256), 0, stream, a);
-    else if (a.x_is_big) hipLaunchKernelGGL((wgrad_parity_f32_kernel<64, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((wgrad_parity_f32_kernel<64, false>), grid, dim3(256), 0, stream, a);
-    return check_launch("wgrad_parity_f32 (four taps per block)");
+  WgradFacts f = {a.bn_in.mode, a.bn_in.C, aligned16(x), aligned16(dy), plan ? plan->tile : -1, plan ? plan->split : 0, xcd_remap_enabled(), true};
+  WgradDecision d;
+  char msg[512];
+  if (int rc = decide_wgrad(CONV_F32, g, f, d, msg, sizeof msg)) { set_error("%s", msg); return rc; }
+  fill_wgrad_args(a, d, g, x, dy, dwp);
+  a.vecI = d.vecI; a.vecJ = d.vecJ; a.fast = d.fast;
+  if (d.atomic && !dwp_is_zero) {
+    if (hipMemsetAsync(dwp, 0, d.dw_bytes, stream) != hipSuccess) { set_error("wgrad memset failed"); return MOPOE_ERR_LAUNCH; }
   }
-  // 7, 8 = tiles 5, 6 with the fp32 products on the bf16 matrix pipe (EMU; plain operand only)
-  const bool wemu = plan && (plan->tile == 7 || plan->tile == 8);
-  if (wemu && a.bn_in.mode != 0) { set_error("wgrad plan: tile %d (split-bf16 products) has no BN-on-load form", plan->tile); return MOPOE_ERR_ARG; }
-  if (plan && (plan->tile == 2 || plan->tile == 6 || plan->tile == 8)) big = false;   // the plan may ask for 64x64 tiles on wide layers too
-  else if (plan && (plan->tile == 5 || plan->tile == 7)) {
-    // (mirrors the tuner, mimic_amd/ops.py: _wgrad_candidates -- the 128 tile is never offered with <= 64 channels on a side)
-    if (!big) { set_error("wgrad plan: tile %d (128x128 on LDS-DMA) needs more than 64 channels on both sides (%d, %d)", plan->tile, g->Cin, g->Cout); return MOPOE_ERR_ARG; }
-  }
-  else if (plan && plan->tile > 2) { set_error("wgrad plan: tile %d (see mopoe_conv_plan in mopoe_hip.h: -1, 0, 2, 5, 6, 7, 8, 9, 10)", plan->tile); return MOPOE_ERR_ARG; }
-  const bool glds = plan && plan->tile >= 5;
-  if (glds && !vec) { set_error("wgrad plan: the LDS-DMA tiles need the vector path (channel counts %% 4 == 0, aligned tensors)"); return MOPOE_ERR_ARG; }
-  const int T = big ? 128 : 64;
-  const int nI = ceil_div(g->Cin, T), nJ = ceil_div(g->Cout, T);
-  a.nJ = nJ;
-  const long tiles = (long)nI * nJ * taps;
-  // split the pixel reduction until ~1024 blocks are in flight, keeping >= 8 K-chunks per block
-  long split = (1024 + tiles - 1) / tiles;
-  if (plan && plan->split > 0) split = plan->split;
-  const int kp = glds ? 32 : BK;                  // pixels per chunk
-  const long max_split = glds ? (a.Ms + 4 * kp - 1) / (4 * kp) : (a.Ms + 8 * BK - 1) / (8 * BK);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  long chunk = (a.Ms + split - 1) / split;
-  chunk = (chunk + kp - 1) / kp * kp;
-  split = (a.Ms + chunk - 1) / chunk;
-  a.chunk = chunk;
-  a.atomic = split > 1;
-  static const bool xcd_remap = !getenv("MOPOE_NO_XCD_REMAP");   // (A/B switch)
-  a.xcd_remap = xcd_remap ? 1 : 0;
-  const size_t bytes = (size_t)taps * g->Cin * g->Cout * sizeof(float);
-  if (a.atomic && !dwp_is_zero) {
-    if (hipMemsetAsync(dwp, 0, bytes, stream) != hipSuccess) { set_error("wgrad memset failed"); return MOPOE_ERR_LAUNCH; }
-  }
-  const double flops = 2.0 * (double)a.Ms * g->Cin * (double)g->Cout * taps;
-  const int spec = a.fast ? (a.bn_in.mode != 0 ? 2 : 1) : 0;
-  const double abytes = ((double)g->N * g->Hs * g->Ws * (g->transposed ? g->Cin : g->Cout)
-                         + (double)g->N * g->Hb * g->Wb * (g->transposed ? g->Cout : g->Cin)) * sizeof(float);   // both operands, once
-  ProfScope prof(stream, flops, wemu ? PROF_F32_WGRAD_GLDS_EMU + (big ? 0 : 1)
-                                : glds ? PROF_F32_WGRAD_GLDS + (big ? 0 : 2) + (a.bn_in.mode != 0 ? 1 : 0)
-                                     : (vec ? PROF_WGRAD_VEC + (big ? 0 : 3) + spec : PROF_WGRAD_SCALAR + (big ? 0 : 1)), abytes);
-  dim3 grid(nI * nJ, taps, (unsigned)split);
-  if (wemu) {
-    if (big) hipLaunchKernelGGL((wgrad_gemm_f32_glds_kernel<128, false, 2, 1>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((wgrad_gemm_f32_glds_kernel<64, false, 4, 1>), grid, dim3(256), 0, stream, a);
-  } else if (glds) {
-    const bool xf = a.bn_in.mode != 0;
-    if (big) {
-      if (xf) hipLaunchKernelGGL((wgrad_gemm_f32_glds_kernel<128, true, 2>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((wgrad_gemm_f32_glds_kernel<128, false, 2>), grid, dim3(256), 0, stream, a);
-    } else {
-      if (xf) hipLaunchKernelGGL((wgrad_gemm_f32_glds_kernel<64, true, 2>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((wgrad_gemm_f32_glds_kernel<64, false, 4>), grid, dim3(256), 0, stream, a);
-    }
-  } else if (vec) {
-    if (big) {
-      if (spec == 1) hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, true, 1>), grid, dim3(256), 0, stream, a);
-      else if (spec == 2) hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, true, 2>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, true, 0>), grid, dim3(256), 0, stream, a);
-    } else {
-      if (spec == 1) hipLaunchKernelGGL((wgrad_gemm_kernel<64, 64, true, 1>), grid, dim3(256), 0, stream, a);
-      else if (spec == 2) hipLaunchKernelGGL((wgrad_gemm_kernel<64, 64, true, 2>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((wgrad_gemm_kernel<64, 64, true, 0>), grid, dim3(256), 0, stream, a);
-    }
-  } else {
-    if (big) hipLaunchKernelGGL((wgrad_gemm_kernel<128, 128, false>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((wgrad_gemm_kernel<64, 64, false>), grid, dim3(256), 0, stream, a);
-  }
-  return check_launch("wgrad_gemm");
+  ProfScope prof(stream, d.flops, d.kind, d.bytes);
+  const dim3 grid(d.gx, d.gy, d.gz);
+#define MOPOE_CASE(R_, ID_, T_, KP_, ST_, STX_, MC_, KIND_) case ID_: launch_##R_<T_, ST_, STX_>(d, grid, stream, a); break;
+  switch (d.t->id) { MOPOE_F32_WGRAD_TILES(MOPOE_CASE) }
+#undef MOPOE_CASE
+  return check_launch(d.route == W_FOUR ? "wgrad_parity_f32 (four taps per block)" : "wgrad_gemm");
 }
+#undef MOPOE_GO

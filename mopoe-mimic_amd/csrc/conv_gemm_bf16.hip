@@ -21,18 +21,12 @@
 // scalar fallback): K channels a multiple of 32, N channels a multiple of 8, 16-byte aligned tensors < 2 GiB.
 #include "gemm_common.hpp"
 
-#ifndef PERSIST_BLOCKS_BF16
-#define PERSIST_BLOCKS_BF16 512   // upper bound on blocks of one launch (see conv_gemm.hip: PERSIST_BLOCKS)
-#endif
-
 namespace mopoe {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-constexpr int BKH = 32;   // K chunk in bf16 elements (two 16-deep MFMA steps); Ck % BKH == 0 is required
 
 struct GemmArgsH {
   const bf16_t* X;       // gathered operand [rows_x][ldx]
@@ -556,171 +550,59 @@ __global__ __launch_bounds__(256) void wgrad_gemm_bf16_kernel(const WgradArgsH a
 #include "conv_gemm_bf16_glds.inc"
 
 // =====================================================================================================
-// host-side launchers
+// host-side launchers: what is launched is decided in conv_launch.hpp (decide_gather / decide_wgrad: the bf16 tile
+// tables and their comments stand there); here the argument struct is filled and the tile's kernel is named
 // =====================================================================================================
-static int ilog2_exact(long v) {
-  if (v <= 0 || (v & (v - 1))) return -1;
-  int l = 0;
-  while ((1L << l) < v) ++l;
-  return l;
-}
+static bool bf16_glds_default() { static const bool on = !getenv("MOPOE_BF16_NO_GLDS"); return on; }   // (A/B switch for the static heuristic)
 
-// tiles: 0 = 128x128 (4 waves)  1 = 256x64 (4 waves)  2 = 64x64 (4 waves)  3 = 256x128 (8 waves)  4 = 128x64 (4 waves)
-// LDS-DMA family (conv_gemm_bf16_glds.inc; operands without a transform on load, K channels a multiple of 64):
-//   5 = 128x128, 2 buffers   6 = 128x128, 3 buffers   7 = 256x128 (8 waves), 2 buffers   8 = 256x128, 3 buffers
-//   9 = 128x64, 2 buffers   10 = 128x64, 3 buffers   11 = 64x64, 4 buffers (the deep layers: few rows, long reductions)
-constexpr int BF16_NTILES = 12;
+#define MOPOE_GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(THREADS), 0, stream, a)
+template <int BM, int BN, int WM, int WN, int ST, bool XF>
+static void launch_HREG(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgsH& a) {
+  constexpr int THREADS = 64 * WM * WN;
+  if (d.spec == 1) MOPOE_GO(gather_gemm_bf16_kernel<BM, BN, WM, WN, 1>);
+  else if (d.spec == 2) MOPOE_GO(gather_gemm_bf16_kernel<BM, BN, WM, WN, 2>);
+  else MOPOE_GO(gather_gemm_bf16_kernel<BM, BN, WM, WN, 3>);
+}
+template <int BM, int BN, int WM, int WN, int ST, bool XF>
+static void launch_HGLDS(const GatherDecision& d, dim3 grid, hipStream_t stream, const GemmArgsH& a) {
+  constexpr int THREADS = 64 * WM * WN;
+  if (d.spec == 1) MOPOE_GO(gather_gemm_bf16_glds_kernel<BM, BN, WM, WN, 1, ST>);
+  else if (d.spec == 3) MOPOE_GO(gather_gemm_bf16_glds_kernel<BM, BN, WM, WN, 3, ST>);
+  else if constexpr (XF) MOPOE_GO(gather_gemm_bf16_glds_kernel<BM, BN, WM, WN, 2, ST>);
+}
+template <int BM, int BN, int WM, int WN, int ST, bool XF>
+static void launch_HNONE(const GatherDecision&, dim3, hipStream_t, const GemmArgsH&) {}   // (refused by the decision)
+
 static int launch_gather_bf16(const bf16_t* X, const bf16_t* W, const float* bias, void* Y, int out_f32,
                               const mopoe_conv_geom* g, int dest_on_small, int Ck, int Cn, int w_nk,
                               const mopoe_bn_ref* bn_in, const mopoe_mask_ref* mask, double* out_stats,
                               const mopoe_bn_ref* relu_bn, const bf16_t* xin, double* bwd_sums,
                               const mopoe_conv_plan* plan, void* ws, size_t ws_bytes, hipStream_t stream,
                               const mopoe_mix_ref* mix = nullptr) {
+  const mopoe_bn_ref none = {};
+  const mopoe_mask_ref nomask = {nullptr, 0, 1};
   GemmArgsH a;
-  a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.out_f32 = out_f32;
-  a.N = g->N; a.Ck = Ck; a.Cn = Cn; a.Cin_w = g->Cin; a.Cout_w = g->Cout;
-  a.ldx = Ck; a.ldy = Cn;
-  a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
-  int nphase;
-  if (dest_on_small) {
-    a.form = 0; a.Hx = g->Hb; a.Wx = g->Wb; a.Hy = g->Hs; a.Wy = g->Ws; a.Hq = g->Hs; a.Wq = g->Ws; nphase = 1;
-  } else {
-    a.form = 1; a.Hx = g->Hs; a.Wx = g->Ws; a.Hy = g->Hb; a.Wy = g->Wb; a.Hq = g->Hb / g->sh; a.Wq = g->Wb / g->sw;
-    nphase = g->sh * g->sw;
-  }
-  a.rows_per_phase = (long)g->N * a.Hq * a.Wq;
-  a.rows_total = (long)g->N * a.Hy * a.Wy;
-  const size_t xb = (size_t)g->N * a.Hx * a.Wx * Ck * sizeof(bf16_t);
-  const size_t wb = (size_t)g->kh * g->kw * g->Cin * g->Cout * sizeof(bf16_t);
-  if (Ck % BKH != 0 || Cn % 8 != 0 || g->Cout % 8 != 0) {
-    set_error("bf16 conv: K channels must be a multiple of 32 and N channels of 8 (Ck = %d, Cn = %d)", Ck, Cn);
-    return MOPOE_ERR_ARG;
-  }
-  if (!aligned16(X) || !aligned16(W) || !aligned16(Y) || (xin && !aligned16(xin)) || xb >= (1ull << 31) || wb >= (1ull << 31)) {
-    set_error("bf16 conv: tensors must be 16-byte aligned and smaller than 2 GiB");
-    return MOPOE_ERR_ARG;
-  }
-  a.x_bytes = (unsigned)xb;
-  a.w_bytes = (unsigned)wb;
-  mopoe_bn_ref none = {};
-  mopoe_mask_ref nomask = {nullptr, 0, 1};
   a.bn_in = bn_in ? *bn_in : none;
   a.mask = mask ? *mask : nomask;
-  a.out_stats = out_stats;
-  a.relu_bn = relu_bn ? *relu_bn : none;
-  a.xin = xin; a.bwd_sums = bwd_sums;
-  a.mix = 0; a.mix_a = a.mix_b = 0.f;
-  static const bool xcd_remap_g = !getenv("MOPOE_NO_XCD_REMAP");   // (A/B switch)
-  a.xcd_remap = xcd_remap_g ? 1 : 0;
-  if (mix) {   // residual mix in the epilogue: the shortcut's BN rides in relu_bn, its (bf16) tensor in xin
-    if (!mix->s || mix->bn.mode == 0 || relu_bn || xin || out_f32 || !aligned16(mix->s)) { set_error("conv_fwd_mix_bf16: needs an aligned bf16 s, its BatchNorm and a bf16 result"); return MOPOE_ERR_ARG; }
-    a.mix = 1; a.mix_a = mix->a; a.mix_b = mix->b;
-    a.relu_bn = mix->bn; a.xin = (const bf16_t*)mix->s;
-  }
-  a.nsplit = 1; a.partial = nullptr; a.counters = nullptr;
-  if (a.bn_in.mode != 0 && (a.bn_in.C != Ck || Ck > MAX_BN_C)) { set_error("bn_in channel mismatch (%d vs %d)", a.bn_in.C, Ck); return MOPOE_ERR_ARG; }
-  if (a.relu_bn.mode != 0 && (a.relu_bn.C != Cn || !a.xin)) { set_error("relu_bn needs xin and C == %d", Cn); return MOPOE_ERR_ARG; }
-  if (a.mask.kind != 0 && !a.mask.mask) { set_error("mask pointer missing"); return MOPOE_ERR_ARG; }
-  if (a.mask.kind == 1 && a.mask.rows_per_sample != a.Hy * a.Wy) { set_error("channel mask: rows_per_sample must be Hout*Wout"); return MOPOE_ERR_ARG; }
-  if (a.rows_total >= (1L << 31) || (long)g->N * a.Hx * a.Wx >= (1L << 31)) { set_error("conv: more than 2^31 rows"); return MOPOE_ERR_ARG; }
-
-  int cfg;
-  if (Cn > 64) cfg = a.rows_per_phase >= 256L * 128 ? 3 : (a.rows_per_phase > 64 ? 0 : 2);
-  else cfg = a.rows_per_phase >= 256L * 64 ? 1 : 2;
-  const bool glds_ok = Ck % 64 == 0;     // (with BN on load: tiles 5, 7, 9 (two buffers) and 11 (four; the three-buffer forms exceed 256 registers))
-  static const bool glds_default = !getenv("MOPOE_BF16_NO_GLDS");   // (A/B switch for the static heuristic)
-  if (glds_ok && glds_default) cfg = cfg == 0 ? 5 : (cfg == 3 ? 7 : (cfg == 4 ? 9 : cfg));
-  if (plan && plan->tile >= 0) {
-    if (plan->tile >= BF16_NTILES) { set_error("bf16 conv plan: tile %d (0..%d)", plan->tile, BF16_NTILES - 1); return MOPOE_ERR_ARG; }
-    // (tile 8 = 256x128 with three buffers spills registers: never offered by the tuner, no longer reachable through a plan)
-    if (plan->tile == 8) { set_error("bf16 conv plan: tile 8 (256x128, three LDS buffers) is not built: it spills registers; use 7"); return MOPOE_ERR_ARG; }
-    if (plan->tile >= 5 && (!glds_ok || (a.bn_in.mode != 0 && (plan->tile == 6 || plan->tile == 8 || plan->tile == 10)))) {
-      set_error("bf16 conv plan: tile %d (LDS-DMA family) needs K channels %% 64 == 0 (Ck = %d) and, with BN on load, one of the tiles 5, 7, 9, 11", plan->tile, Ck);
-      return MOPOE_ERR_ARG;
-    }
-    cfg = plan->tile;
-  }
-  static const int TILE_BM[BF16_NTILES] = {128, 256, 64, 256, 128, 128, 128, 256, 256, 128, 128, 64};
-  static const int TILE_BN[BF16_NTILES] = {128, 64, 64, 128, 64, 128, 128, 128, 128, 64, 64, 64};
-  const int bm = TILE_BM[cfg], bn = TILE_BN[cfg];
-  const long nMt = ceil_div(a.rows_per_phase, bm);
-  const int nNt = ceil_div(Cn, bn);
-  const int nkc = Ck / (cfg >= 5 ? 64 : BKH);    // K chunks per tap (the LDS-DMA tiles walk K 64 deep)
-  const int iters = (dest_on_small ? g->kh * g->kw : std::max(1, (g->kh / g->sh) * (g->kw / g->sw))) * nkc;
-  const long blocks = nMt * nNt * nphase;
-  const size_t per = (size_t)a.rows_total * Cn * sizeof(float);
-  // workspace = [arrival counters: WS_COUNTER_BYTES, zero between launches][fp32 slabs]
-  const bool can_split = ws && ws_bytes > WS_COUNTER_BYTES && blocks <= (long)(WS_COUNTER_BYTES / sizeof(int));
-  const size_t slab_bytes = can_split ? ws_bytes - WS_COUNTER_BYTES : 0;
-  long ns = 1;
-  if (plan && plan->split > 0) {
-    ns = std::min<long>(plan->split, iters);
-    if (ns >= 2 && (!can_split || (size_t)ns * per > slab_bytes)) {
-      set_error("bf16 conv plan: split %ld needs %zu workspace bytes (have %zu) and at most %zu output tiles (have %ld)", ns,
-                (size_t)ns * per + WS_COUNTER_BYTES, ws ? ws_bytes : (size_t)0, WS_COUNTER_BYTES / sizeof(int), blocks);
-      return MOPOE_ERR_ARG;
-    }
-  } else if (can_split && blocks < 256 && iters >= 8) {
-    ns = std::min<long>((512 + blocks - 1) / blocks, (long)iters / 4);
-    if ((size_t)ns * per > slab_bytes) ns = (long)(slab_bytes / per);
-  }
-  if (ns >= 2) {
-    a.nsplit = (int)ns;
-    a.counters = (int*)ws;
-    a.partial = (float*)((char*)ws + WS_COUNTER_BYTES);
-  }
-  // resident blocks: 8-wave tiles 2 per CU, 4-wave register-staged tiles 3 per CU; the LDS-DMA tiles by their LDS footprint
-  // (64 KB -> 2 per CU, 48 KB -> 3 per CU, 96 KB and more -> 1 per CU)
-  static const int GLDS_PER_CU[BF16_NTILES] = {0, 0, 0, 0, 0, 2, 1, 1, 1, 3, 2, 2};
-  const long persist = cfg >= 5 ? 256L * GLDS_PER_CU[cfg] : (cfg == 3 ? PERSIST_BLOCKS_BF16 : PERSIST_BLOCKS_BF16 * 3 / 2);
-  long gx = std::min<long>(nMt, std::max<long>(1, persist / ((long)nNt * nphase * a.nsplit)));
-  const double taps_eff = dest_on_small ? (double)g->kh * g->kw : (double)g->kh * g->kw / ((double)g->sh * g->sw);
-  const double flops = 2.0 * (double)g->N * a.Hy * a.Wy * (double)Cn * (double)Ck * taps_eff;
-  {
-    const int spec = w_nk ? 3 : (a.bn_in.mode != 0 ? 2 : 1);
-    const double abytes = (double)xb + (double)a.rows_total * Cn * (out_f32 ? 4.0 : 2.0);
-    static const int GLDS_X_SLOT[BF16_NTILES] = {0, 0, 0, 0, 0, 0, 0, 1, 0, 2, 3, 4};
-    ProfScope prof(stream, flops, cfg >= 5 ? (spec == 2 ? PROF_BF16_GLDS_X + GLDS_X_SLOT[cfg] : PROF_BF16_GLDS + (cfg - 5) * 2 + (spec == 3 ? 1 : 0))
-                                           : PROF_BF16_GATHER + cfg * 3 + (spec - 1), abytes);
-    dim3 grid((unsigned)gx, nNt, nphase * a.nsplit);
-#define MOPOE_LAUNCH_G(BM_, BN_, WM_, WN_, ST_)                                                                                           \
-  do {                                                                                                                                  \
-    if (spec == 1) hipLaunchKernelGGL((gather_gemm_bf16_glds_kernel<BM_, BN_, WM_, WN_, 1, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a); \
-    else hipLaunchKernelGGL((gather_gemm_bf16_glds_kernel<BM_, BN_, WM_, WN_, 3, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a);          \
-  } while (0)
-#define MOPOE_LAUNCH_GX(BM_, BN_, WM_, WN_, ST_) hipLaunchKernelGGL((gather_gemm_bf16_glds_kernel<BM_, BN_, WM_, WN_, 2, ST_>), grid, dim3(64 * WM_ * WN_), 0, stream, a)
-    if (cfg >= 5) {
-      if (spec == 2) {
-        if (cfg == 5) MOPOE_LAUNCH_GX(128, 128, 2, 2, 2);
-        else if (cfg == 7) MOPOE_LAUNCH_GX(256, 128, 4, 2, 2);
-        else if (cfg == 9) MOPOE_LAUNCH_GX(128, 64, 4, 1, 2);
-        else MOPOE_LAUNCH_GX(64, 64, 2, 2, 4);
-      }
-      else if (cfg == 5) MOPOE_LAUNCH_G(128, 128, 2, 2, 2);
-      else if (cfg == 6) MOPOE_LAUNCH_G(128, 128, 2, 2, 3);
-      else if (cfg == 7) MOPOE_LAUNCH_G(256, 128, 4, 2, 2);
-      else if (cfg == 9) MOPOE_LAUNCH_G(128, 64, 4, 1, 2);
-      else if (cfg == 10) MOPOE_LAUNCH_G(128, 64, 4, 1, 3);
-      else MOPOE_LAUNCH_G(64, 64, 2, 2, 4);
-      if (int rc = check_launch("gather_gemm_bf16_glds")) return rc;
-      return MOPOE_OK;
-    }
-#undef MOPOE_LAUNCH_G
-#define MOPOE_LAUNCH_H(BM_, BN_, WM_, WN_)                                                                                          \
-  do {                                                                                                                            \
-    if (spec == 1) hipLaunchKernelGGL((gather_gemm_bf16_kernel<BM_, BN_, WM_, WN_, 1>), grid, dim3(64 * WM_ * WN_), 0, stream, a);      \
-    else if (spec == 2) hipLaunchKernelGGL((gather_gemm_bf16_kernel<BM_, BN_, WM_, WN_, 2>), grid, dim3(64 * WM_ * WN_), 0, stream, a); \
-    else hipLaunchKernelGGL((gather_gemm_bf16_kernel<BM_, BN_, WM_, WN_, 3>), grid, dim3(64 * WM_ * WN_), 0, stream, a);                \
-  } while (0)
-    if (cfg == 0) MOPOE_LAUNCH_H(128, 128, 2, 2);
-    else if (cfg == 1) MOPOE_LAUNCH_H(256, 64, 4, 1);
-    else if (cfg == 3) MOPOE_LAUNCH_H(256, 128, 4, 2);
-    else if (cfg == 4) MOPOE_LAUNCH_H(128, 64, 4, 1);
-    else MOPOE_LAUNCH_H(64, 64, 2, 2);
-#undef MOPOE_LAUNCH_H
-    if (int rc = check_launch("gather_gemm_bf16")) return rc;
-  }
-  return MOPOE_OK;
+  // residual mix in the epilogue: the shortcut's BN rides in relu_bn, its (bf16) tensor in xin
+  a.relu_bn = mix ? mix->bn : (relu_bn ? *relu_bn : none);
+  a.xin = mix ? (const bf16_t*)mix->s : xin;
+  GatherFacts f = {dest_on_small, Ck, Cn, w_nk, a.bn_in.mode, a.bn_in.C, a.relu_bn.mode, a.relu_bn.C, a.xin != nullptr,
+                   a.mask.kind, a.mask.mask != nullptr, a.mask.rows_per_sample, mix != nullptr, mix && mix->s && mix->bn.mode != 0, out_f32 != 0,
+                   aligned16(X), aligned16(W), aligned16(Y), aligned16(xin), true, mix && aligned16(mix->s),
+                   plan ? plan->tile : -1, plan ? plan->split : 0, ws != nullptr, ws_bytes, xcd_remap_enabled(), bf16_glds_default()};
+  GatherDecision d;
+  char msg[512];
+  if (int rc = decide_gather(CONV_BF16, g, f, d, msg, sizeof msg)) { set_error("%s", msg); return rc; }
+  fill_gather_args(a, d, g, X, W, bias, Y, Ck, Cn, out_stats, bwd_sums, mix, ws);
+  a.out_f32 = out_f32; a.ldx = Ck; a.ldy = Cn;
+  ProfScope prof(stream, d.flops, d.kind, d.bytes);
+  const dim3 grid((unsigned)d.gx, d.nNt, d.nphase * d.nsplit);
+#define MOPOE_CASE(K_, ID_, BM_, BN_, WM_, WN_, BK_, ST_, P_, X_, KIND_, KINDX_) \
+  case ID_: launch_##K_<BM_, BN_, WM_, WN_, ST_, X_>(d, grid, stream, a); break;
+  switch (d.t->id) { MOPOE_BF16_GATHER_TILES(MOPOE_CASE) }
+#undef MOPOE_CASE
+  return check_launch(d.t->kernel == G_HGLDS ? "gather_gemm_bf16_glds" : "gather_gemm_bf16");
 }
 
 }  // namespace mopoe
@@ -757,148 +639,65 @@ extern "C" int mopoe_conv_dgrad_bf16(const uint16_t* dy, const uint16_t* wp, voi
                             nullptr, nullptr, relu_bn, xin, bwd_sums, plan, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+template <int T, int ST, int STX>
+static void launch_W_REG(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgsH& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (d.bn_on_load && d.fast) MOPOE_GO(wgrad_gemm_bf16_kernel<T, T, true, true>);
+  else if (d.bn_on_load) MOPOE_GO(wgrad_gemm_bf16_kernel<T, T, true, false>);
+  else if (d.fast) MOPOE_GO(wgrad_gemm_bf16_kernel<T, T, false, true>);
+  else MOPOE_GO(wgrad_gemm_bf16_kernel<T, T, false, false>);
+}
+template <int T, int ST, int STX>
+static void launch_W_GLDS(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgsH& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (d.bn_on_load && d.fast) MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, true, true>);
+  else if (d.bn_on_load) MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, true, false>);
+  else if (d.fast) MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, false, true>);
+  else MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, false, false>);
+}
+template <int T, int ST, int STX>
+static void launch_W_MERGE(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgsH& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (d.merge == 1 && d.fast) MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, false, true, 1>);
+  else if (d.merge == 1) MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, false, false, 1>);
+  else if (d.fast) MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, false, true, 2>);
+  else MOPOE_GO(wgrad_gemm_bf16_glds_kernel<T, false, false, 2>);
+}
+template <int T, int ST, int STX>
+static void launch_W_FOUR(const WgradDecision& d, dim3 grid, hipStream_t stream, const WgradArgsH& a) {
+  constexpr int THREADS = WGRAD_THREADS;
+  if (d.x_is_big) MOPOE_GO(wgrad_parity_bf16_kernel<T, true>);
+  else MOPOE_GO(wgrad_parity_bf16_kernel<T, false>);
+}
+
 extern "C" int mopoe_conv_wgrad_bf16(const uint16_t* x, const uint16_t* dy, float* dwp, const mopoe_conv_geom* g,
                                      const mopoe_bn_ref* bn_in, int32_t dwp_is_zero, const mopoe_conv_plan* plan,
                                      void* stream_) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !dy || !dwp) { set_error("conv_wgrad_bf16: null pointer"); return MOPOE_ERR_ARG; }
   hipStream_t stream = (hipStream_t)stream_;
+  const mopoe_bn_ref none = {};
   WgradArgsH a;
-  a.Xs = x; a.Dy = dy; a.dW = dwp;
-  a.N = g->N; a.Hs = g->Hs; a.Ws = g->Ws; a.Hb = g->Hb; a.Wb = g->Wb; a.Cin = g->Cin; a.Cout = g->Cout;
-  a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
-  a.x_is_big = g->transposed ? 0 : 1;
-  a.Ms = (long)g->N * g->Hs * g->Ws;
-  mopoe_bn_ref none = {};
   a.bn_in = bn_in ? *bn_in : none;
-  if (a.bn_in.mode != 0 && (a.bn_in.C != g->Cin || g->Cin > MAX_BN_C)) { set_error("wgrad bn_in channel mismatch"); return MOPOE_ERR_ARG; }
-  if (g->Cin % 8 != 0 || g->Cout % 8 != 0) { set_error("bf16 wgrad: channel counts must be multiples of 8 (%d, %d)", g->Cin, g->Cout); return MOPOE_ERR_ARG; }
-  const size_t rows_x = (size_t)g->N * (g->transposed ? g->Hs * g->Ws : g->Hb * g->Wb);
-  const size_t rows_dy = (size_t)g->N * (g->transposed ? g->Hb * g->Wb : g->Hs * g->Ws);
-  const size_t xb = rows_x * g->Cin * sizeof(bf16_t), db = rows_dy * g->Cout * sizeof(bf16_t);
-  if (!aligned16(x) || !aligned16(dy) || xb >= (1ull << 31) || db >= (1ull << 31)) {
-    set_error("bf16 wgrad: tensors must be 16-byte aligned and smaller than 2 GiB");
-    return MOPOE_ERR_ARG;
+  WgradFacts f = {a.bn_in.mode, a.bn_in.C, aligned16(x), aligned16(dy), plan ? plan->tile : -1, plan ? plan->split : 0, xcd_remap_enabled(), bf16_glds_default()};
+  WgradDecision d;
+  char msg[512];
+  if (int rc = decide_wgrad(CONV_BF16, g, f, d, msg, sizeof msg)) { set_error("%s", msg); return rc; }
+  fill_wgrad_args(a, d, g, x, dy, dwp);
+  a.lg_ws = d.lg_ws; a.lg_hw = d.lg_hw;
+  if (d.atomic && !dwp_is_zero) {
+    if (hipMemsetAsync(dwp, 0, d.dw_bytes, stream) != hipSuccess) { set_error("wgrad memset failed"); return MOPOE_ERR_LAUNCH; }
   }
-  a.x_bytes = (unsigned)xb;
-  a.dy_bytes = (unsigned)db;
-  a.lg_ws = ilog2_exact(g->Ws);
-  a.lg_hw = ilog2_exact((long)g->Hs * g->Ws);
-  const bool pow2 = a.lg_ws >= 0 && a.lg_hw >= 0;
-  const int taps = g->kh * g->kw;
-  bool big = g->Cin > 64 && g->Cout > 64;
-  if (plan && (plan->tile == 2 || plan->tile == 6)) big = false;
-  if (plan && plan->tile == 5) {
-    // the 128 x 128 LDS-DMA tile on a layer with <= 64 channels on one side would run half-empty MFMA tiles: refused, as the
-    // tuner never offers it (mimic_amd/ops.py: _wgrad_candidates)
-    if (!big) { set_error("bf16 wgrad plan: tile 5 (128x128 on LDS-DMA) needs more than 64 channels on both sides (%d, %d)", g->Cin, g->Cout); return MOPOE_ERR_ARG; }
-  }
-  // plan tiles: 0 = 128x128, 2 = 64x64 (register-staged, 32 pixels per chunk); 5 = 128x128, 6 = 64x64 on LDS-DMA (64 pixels
-  // per stage).  Default: the LDS-DMA form (MOPOE_BF16_NO_GLDS = the register-staged one).
-  static const bool glds_default = !getenv("MOPOE_BF16_NO_GLDS");
-  const bool glds = plan && plan->tile >= 0 ? plan->tile >= 5 : glds_default;
-  // tile 7: the 128 tile on LDS-DMA with TWO taps per block on the side of the gathered operand when that side has 64 channels
-  // (conv_gemm_bf16_glds.inc, MERGE): convs with Cin = 64 (1), transposed convs with Cout = 64 (2); plain operands, even tap count
-  const bool xf_ = a.bn_in.mode != 0;
-  const int merge_ok = (!xf_ && taps % 2 == 0) ? (a.x_is_big ? (g->Cin == 64 ? 1 : 0) : (g->Cout == 64 ? 2 : 0)) : 0;
-  if (plan && plan->tile > 9) { set_error("bf16 wgrad plan: tile %d (0, 2, 5, 6, 7, 8, 9)", plan->tile); return MOPOE_ERR_ARG; }
-  // tiles 8 / 9: four taps (one parity class of a k4 s2 p1 kernel) per block, 64 gathered channels x 64 / 128 channels of the
-  // small-grid operand (conv_gemm_bf16_glds.inc: wgrad_parity_bf16_kernel)
-  if (plan && plan->tile >= 8) {
-    const bool ok = !xf_ && g->kh == 4 && g->kw == 4 && g->sh == 2 && g->sw == 2 && g->ph == 1 && g->pw == 1 &&
-                    g->Hs % 8 == 0 && g->Ws % 8 == 0 && g->Hb == 2 * g->Hs && g->Wb == 2 * g->Ws;
-    if (!ok) {
-      set_error("bf16 wgrad plan: tiles 8 / 9 (four taps per block) need a plain operand, k4 s2 p1 and a small grid of whole 8 x 8 tiles");
-      return MOPOE_ERR_ARG;
-    }
-    const int Cg = a.x_is_big ? g->Cin : g->Cout, Csm = a.x_is_big ? g->Cout : g->Cin;
-    const int cs = plan->tile == 9 ? 128 : 64;
-    if (cs == 128 && Csm % 128 != 0) { set_error("bf16 wgrad plan: tile 9 needs a multiple of 128 channels on the small-grid operand"); return MOPOE_ERR_ARG; }
-    const long ntiles = (long)g->N * (g->Hs / 8) * (g->Ws / 8);
-    const long cblocks = (long)ceil_div(Cg, 64) * ceil_div(Csm, cs) * 4;
-    long split = plan->split > 0 ? plan->split : (512 + cblocks - 1) / cblocks;
-    if (split > ntiles) split = ntiles;
-    if (split < 1) split = 1;
-    a.chunk = (ntiles + split - 1) / split;             // (in 8 x 8 tiles)
-    split = (ntiles + a.chunk - 1) / a.chunk;
-    a.atomic = split > 1;
-    static const bool xcd_remap8 = !getenv("MOPOE_NO_XCD_REMAP");
-    a.xcd_remap = xcd_remap8 ? 1 : 0;
-    if (a.atomic && !dwp_is_zero) {
-      if (hipMemsetAsync(dwp, 0, (size_t)taps * g->Cin * g->Cout * sizeof(float), stream) != hipSuccess) { set_error("wgrad memset failed"); return MOPOE_ERR_LAUNCH; }
-    }
-    ProfScope prof(stream, 2.0 * (double)a.Ms * g->Cin * (double)g->Cout * taps, PROF_BF16_WGRAD_PARITY + (cs == 128 ? 1 : 0), (double)xb + (double)db);
-    const dim3 grid((unsigned)(ceil_div(Cg, 64) * ceil_div(Csm, cs)), 4, (unsigned)split);
-    if (cs == 128 && a.x_is_big) hipLaunchKernelGGL((wgrad_parity_bf16_kernel<128, true>), grid, dim3(256), 0, stream, a);
-    else if (cs == 128) hipLaunchKernelGGL((wgrad_parity_bf16_kernel<128, false>), grid, dim3(256), 0, stream, a);
-    else if (a.x_is_big) hipLaunchKernelGGL((wgrad_parity_bf16_kernel<64, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((wgrad_parity_bf16_kernel<64, false>), grid, dim3(256), 0, stream, a);
-    return check_launch("wgrad_parity_bf16 (four taps per block)");
-  }
-  if (plan && plan->tile == 7 && !merge_ok) {
-    set_error("bf16 wgrad plan: tile 7 (two taps per block) needs a plain operand, an even tap count and 64 channels on the gathered side");
-    return MOPOE_ERR_ARG;
-  }
-  const int merge = plan && plan->tile == 7 ? merge_ok : 0;
-  if (merge) big = true;
-  const int T = big ? 128 : 64;
-  const int nI = merge == 1 ? 1 : ceil_div(g->Cin, T), nJ = merge == 2 ? 1 : ceil_div(g->Cout, T);
-  a.nJ = nJ;
-  const long tiles = (long)nI * nJ * (merge ? taps / 2 : taps);
-  long split = (1024 + tiles - 1) / tiles;
-  if (plan && plan->split > 0) split = plan->split;
-  const int kp = glds ? 64 : BKH;                 // pixels per chunk
-  const long max_split = (a.Ms + 4 * kp - 1) / (4 * kp);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  long chunk = (a.Ms + split - 1) / split;
-  chunk = (chunk + kp - 1) / kp * kp;
-  split = (a.Ms + chunk - 1) / chunk;
-  a.chunk = chunk;
-  a.atomic = split > 1;
-  static const bool xcd_remap = !getenv("MOPOE_NO_XCD_REMAP");   // (A/B switch)
-  a.xcd_remap = xcd_remap ? 1 : 0;
-  const size_t bytes = (size_t)taps * g->Cin * g->Cout * sizeof(float);
-  if (a.atomic && !dwp_is_zero) {
-    if (hipMemsetAsync(dwp, 0, bytes, stream) != hipSuccess) { set_error("wgrad memset failed"); return MOPOE_ERR_LAUNCH; }
-  }
-  const double flops = 2.0 * (double)a.Ms * g->Cin * (double)g->Cout * taps;
-  const bool xf = a.bn_in.mode != 0;
-  ProfScope prof(stream, flops, merge ? PROF_BF16_WGRAD_GLDS_MERGE + merge - 1
-                                      : (glds ? PROF_BF16_WGRAD_GLDS : PROF_BF16_WGRAD) + (big ? 0 : 2) + (xf ? 1 : 0), (double)xb + (double)db);
-  dim3 grid(nI * nJ, merge ? taps / 2 : taps, (unsigned)split);
-  if (merge) {
-    if (merge == 1 && pow2) hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<128, false, true, 1>), grid, dim3(256), 0, stream, a);
-    else if (merge == 1) hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<128, false, false, 1>), grid, dim3(256), 0, stream, a);
-    else if (pow2) hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<128, false, true, 2>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<128, false, false, 2>), grid, dim3(256), 0, stream, a);
-    return check_launch("wgrad_gemm_bf16_glds (two taps per block)");
-  }
-  if (glds) {
-#define MOPOE_LAUNCH_WG(T_)                                                                                             \
-  do {                                                                                                                 \
-    if (xf && pow2) hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<T_, true, true>), grid, dim3(256), 0, stream, a);      \
-    else if (xf) hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<T_, true, false>), grid, dim3(256), 0, stream, a);        \
-    else if (pow2) hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<T_, false, true>), grid, dim3(256), 0, stream, a);      \
-    else hipLaunchKernelGGL((wgrad_gemm_bf16_glds_kernel<T_, false, false>), grid, dim3(256), 0, stream, a);               \
-  } while (0)
-    if (big) MOPOE_LAUNCH_WG(128);
-    else MOPOE_LAUNCH_WG(64);
-#undef MOPOE_LAUNCH_WG
-    return check_launch("wgrad_gemm_bf16_glds");
-  }
-#define MOPOE_LAUNCH_WH(T_)                                                                                              \
-  do {                                                                                                                 \
-    if (xf && pow2) hipLaunchKernelGGL((wgrad_gemm_bf16_kernel<T_, T_, true, true>), grid, dim3(256), 0, stream, a);        \
-    else if (xf) hipLaunchKernelGGL((wgrad_gemm_bf16_kernel<T_, T_, true, false>), grid, dim3(256), 0, stream, a);          \
-    else if (pow2) hipLaunchKernelGGL((wgrad_gemm_bf16_kernel<T_, T_, false, true>), grid, dim3(256), 0, stream, a);        \
-    else hipLaunchKernelGGL((wgrad_gemm_bf16_kernel<T_, T_, false, false>), grid, dim3(256), 0, stream, a);                 \
-  } while (0)
-  if (big) MOPOE_LAUNCH_WH(128);
-  else MOPOE_LAUNCH_WH(64);
-#undef MOPOE_LAUNCH_WH
-  return check_launch("wgrad_gemm_bf16");
+  ProfScope prof(stream, d.flops, d.kind, d.bytes);
+  const dim3 grid(d.gx, d.gy, d.gz);
+#define MOPOE_CASE(R_, ID_, T_, KP_, ST_, STX_, MC_, KIND_) case ID_: launch_##R_<T_, ST_, STX_>(d, grid, stream, a); break;
+  switch (d.t->id) { MOPOE_BF16_WGRAD_TILES(MOPOE_CASE) }
+#undef MOPOE_CASE
+  return check_launch(d.route == W_FOUR ? "wgrad_parity_bf16 (four taps per block)"
+                      : d.route == W_MERGE ? "wgrad_gemm_bf16_glds (two taps per block)"
+                      : d.route == W_GLDS ? "wgrad_gemm_bf16_glds" : "wgrad_gemm_bf16");
 }
+#undef MOPOE_GO
 
 // ---- image-side edge layers with the wide tensor in bf16 (the single-channel image, the taps and the tap gradients
 // stay fp32): stem forward / head input gradient, stem / head weight gradient, head forward ------------------------------

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "conv_launch.hpp"
 
 namespace mopoe {
 
@@ -18,13 +19,9 @@ template <typename T> int edge_reduce(const T* x, const float* W, const float* b
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int MAX_BN_C = 1024;
 // voffset past every buffer (operands are < 2 GiB, checked on the host): the hardware range check returns zeros.
 // 2^31 rather than ~0 so that voffset + soffset cannot wrap whichever of the two the range check includes.
 constexpr unsigned OOB = 0x80000000u;
-constexpr size_t WS_RECOMMENDED = 64u << 20;
-// head of the conv workspace: one int arrival counter per output tile of a split reduction (zero between launches)
-constexpr size_t WS_COUNTER_BYTES = 64u << 10;
 
 // ---- which taps a block multiplies, and from where --------------------------------------------------------------
 // form 0: every tap, source pixel = output pixel * stride - pad + tap.  form 1 (sub-pixel phase `phase` of the big
@@ -55,6 +52,37 @@ __device__ __forceinline__ TapWalk tap_walk(const Args& a, int phase) {
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// XCD-aware block numbering (xcd_swizzle below) unless the A/B switch is set
+static inline bool xcd_remap_enabled() { static const bool on = !getenv("MOPOE_NO_XCD_REMAP"); return on; }
+
+// the fields GemmArgs / GemmArgsH and WgradArgs / WgradArgsH share, from the geometry and the launch decision (conv_launch.hpp)
+template <typename Args, typename T, typename TY>
+static inline void fill_gather_args(Args& a, const GatherDecision& d, const mopoe_conv_geom* g, const T* X, const T* W, const float* bias, TY* Y,
+                                    int Ck, int Cn, double* out_stats, double* bwd_sums, const mopoe_mix_ref* mix, void* ws) {
+  a.X = X; a.W = W; a.Y = Y; a.bias = bias;
+  a.N = g->N; a.Ck = Ck; a.Cn = Cn; a.Cin_w = g->Cin; a.Cout_w = g->Cout;
+  a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
+  a.form = d.form; a.Hx = d.Hx; a.Wx = d.Wx; a.Hy = d.Hy; a.Wy = d.Wy; a.Hq = d.Hq; a.Wq = d.Wq;
+  a.rows_per_phase = d.rows_per_phase; a.rows_total = d.rows_total;
+  a.x_bytes = d.x_bytes; a.w_bytes = d.w_bytes;
+  a.out_stats = out_stats; a.bwd_sums = bwd_sums;
+  a.mix = mix ? 1 : 0; a.mix_a = mix ? mix->a : 0.f; a.mix_b = mix ? mix->b : 0.f;
+  a.xcd_remap = d.xcd_remap;
+  // workspace = [arrival counters of in-kernel split reductions: WS_COUNTER_BYTES, kept zero by the kernels][fp32 slabs]
+  a.nsplit = d.nsplit;
+  a.partial = d.reduce != REDUCE_NONE ? (float*)((char*)ws + d.slab_offset) : nullptr;
+  a.counters = d.reduce == REDUCE_IN_KERNEL ? (int*)ws : nullptr;
+}
+template <typename Args, typename T>
+static inline void fill_wgrad_args(Args& a, const WgradDecision& d, const mopoe_conv_geom* g, const T* x, const T* dy, float* dwp) {
+  a.Xs = x; a.Dy = dy; a.dW = dwp;
+  a.N = g->N; a.Hs = g->Hs; a.Ws = g->Ws; a.Hb = g->Hb; a.Wb = g->Wb; a.Cin = g->Cin; a.Cout = g->Cout;
+  a.kh = g->kh; a.kw = g->kw; a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw;
+  a.x_is_big = d.x_is_big; a.Ms = d.Ms;
+  a.x_bytes = d.x_bytes; a.dy_bytes = d.dy_bytes;
+  a.nJ = d.nJ; a.chunk = d.chunk; a.atomic = d.atomic;
+  a.xcd_remap = d.xcd_remap;
+}
 
 static inline int validate_geom(const mopoe_conv_geom* g) {
   if (!g || g->N <= 0 || g->Hs <= 0 || g->Ws <= 0 || g->Hb <= 0 || g->Wb <= 0 || g->Cin <= 0 || g->Cout <= 0 ||

@@ -7,7 +7,9 @@ entry at its own layer geometry, with the batch reduced to the smallest one that
   * gather_path / wgrad_path: a host-side restatement of what the library does with a plan (csrc/conv_gemm.hip,
     conv_gemm_bf16.hip: launch_gather, mopoe_conv_wgrad*): edge-kernel routing, vector / scalar decision, the tile after the
     fall-backs, fast addressing, four-tap eligibility, the effective split, refusals.  tests/test_plan_table_cpu.py asserts
-    with it that the reduced batch keeps every one of these;
+    with it that the reduced batch keeps every one of these.  The restatement is independent of the library on purpose:
+    tests/test_conv_launch_cpu.py checks it against the decision functions the launchers run (csrc/conv_launch.hpp), on every
+    case of the table and on a sweep of tiles, splits, fusions and geometries the table does not reach;
   * reduced_batch: the rule itself (see its docstring);
   * all_cases(): the case list (table entries, remapped plans, opposite-mask forms, mode-3 input gradients), grouped so that
     cases of one (storage family, layer shape, batch) share x, w, dy and the fp64 evaluations of the convolutions;
@@ -30,7 +32,7 @@ from mimic_amd.ops import Bn, Geom, Mask
 
 BF = torch.bfloat16
 ULP = 2.0 ** -7                       # one bf16 rounding step, relative (tests/test_bf16_gpu.py)
-WS_BYTES = 64 << 20                   # WS_RECOMMENDED (csrc/gemm_common.hpp); the CPU file checks it against the library
+WS_BYTES = 64 << 20                   # WS_RECOMMENDED (csrc/conv_launch.hpp); the CPU file checks it against the library
 WS_COUNTER_BYTES = ops.WS_COUNTER_BYTES
 MIN_ROWS = 1025                       # four 256-row tiles and a one-row tail
 GEOM_FIELDS = ("N", "Hs", "Ws", "Hb", "Wb", "Cin", "Cout", "kh", "kw", "sh", "sw", "ph", "pw", "transposed")
