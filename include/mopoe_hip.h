@@ -565,7 +565,7 @@ int mopoe_adam_step(const mopoe_adam_seg* segs, int32_t nseg, float* step, const
  *   60..74 gather_gemm_bf16_kernel: tile * 3 + (spec - 1)   (tiles 0..4 of the bf16 family)
  *   75..78 wgrad_gemm_bf16_kernel: (128x128 ? 0 : 2) + (BN+ReLU on x ? 1 : 0)
  *   80..93 gather_gemm_bf16_glds_kernel, plain operand: (tile - 5) * 2 + (input gradient ? 1 : 0)   (bf16 tiles 5..11)
- *   94..98 gather_gemm_bf16_glds_kernel with BN+ReLU on load: tiles 5, 7, 9, 10, 11 -> 94..98
+ *   94..98 gather_gemm_bf16_glds_kernel with BN+ReLU on load: tiles 5, 7, 9, 11 -> 94, 95, 96, 98   (97: no kernel)
  *   100..103 wgrad_gemm_bf16_glds_kernel: (128x128 ? 0 : 2) + (BN+ReLU on x ? 1 : 0)
  *   104..115 gather_gemm_f32_glds_kernel: (tile - 12) * 3 + (spec - 1)   (fp32 tiles 12..15)
  *   116..119 wgrad_gemm_f32_glds_kernel: (128x128 ? 0 : 2) + (BN+ReLU on x ? 1 : 0)

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from functools import lru_cache
 from typing import Optional, Sequence
@@ -262,16 +263,121 @@ TUNE_ALPHA = float(os.environ.get("MOPOE_TUNE_ALPHA", "0.7"))
 DIRECT_TILES = os.environ.get("MOPOE_DIRECT_TILES", "0") != "0"
 _conv_calls = 0
 _plans = {}
-_GATHER_TILES = ((128, 128), (256, 64), (64, 64), (256, 128), (128, 64), (64, 64), (128, 64), (128, 128),
-                 (128, 128), (256, 64), (64, 64), (128, 64),   # 8..11: the LDS-free kernel
-                 (128, 128), (128, 64), (64, 64), (256, 128),  # 12..15: the LDS-DMA family (csrc/conv_gemm_glds.inc)
-                 (128, 128), (128, 64), (64, 64), (256, 128))  # 16..19: the same with the fp32 products on the bf16 matrix pipe
 F32_GLDS = os.environ.get("MOPOE_F32_GLDS", "1") != "0"       # A/B switch: keep the tuner off the LDS-DMA tiles
 # A/B switch: tiles 16..19 (plain operand) offered.  The products are the same fp32 numbers -- each operand is split exactly
 # into three bf16 parts and six of the nine partial products are accumulated in fp32 by v_mfma_f32_32x32x16_bf16; the error
 # against fp64 is lower than that of v_mfma_f32_32x32x2_f32 (csrc/conv_gemm_glds.inc, tests: test_f32_products_on_the_bf16_pipe)
 F32_SPLIT_BF16 = os.environ.get("MOPOE_F32_SPLIT_BF16", "1") != "0"
+BF16_GLDS = os.environ.get("MOPOE_BF16_GLDS", "1") != "0"      # A/B switch: keep the tuner on the register-staged tiles
+WGRAD_PARITY = os.environ.get("MOPOE_WGRAD_PARITY", "1") != "0"  # A/B switch: wgrad tile 8 (four taps per block) offered
 _SPLITS = (2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128)
+
+# ---- the conv tiles: one table per family with every fact the tuner, the F32_SPLIT_BF16 remap and the profiling names need,
+# once per tile.  The rows restate csrc/conv_launch.hpp (MOPOE_*_TILES); tests/test_conv_launch_cpu.py holds them against that
+# header, tests/test_abi_cpu.py the names built from them against the kernels of the built library.
+#   kernel      GatherKernel of the header without its G_ (HNONE: a number kept for a tile that is not built)
+#   targs       template arguments of the instantiations, {} = spec: 1 forward, plain operand | 2 forward, BN -> ReLU on load |
+#               3 input gradient | 0 run-time flags (K no multiple of the chunk); scalar_targs: the scalar-path form
+#   k_multiple  the tile is offered only where the K channels are a multiple of this (its K chunk; 1: any K)
+#   vec_only    no scalar-path form: channel counts % 4 == 0;  switches: the A/B switches above that must all be on
+#   bn_form     a BN -> ReLU-on-load instantiation exists (else: plain operands only)
+#   kind        first profiling kind; kind_bn: the BN-on-load form of a bf16 LDS-DMA tile
+#   tuner_resident  blocks the TUNER takes to fill the chip: the denominator of the occupancy term of its objective.  NOT the
+#               header's `persist`, the launcher's cap on a persistent grid (2048 / 3072 on the fp32 register-staged tiles where
+#               this says 512 / 768).  The committed plans were ranked with these numbers: do not "correct" them
+#   twin        with F32_SPLIT_BF16 off, the tile a committed plan on this one is launched as
+_GatherTile = namedtuple("_GatherTile", "kernel id bm bn targs k_multiple vec_only switches bn_form kind tuner_resident "
+                                        "scalar_targs kind_bn twin", defaults=(None, None, None))
+_F32_GATHER_TILES = (
+    _GatherTile("LDS_S", 0, 128, 128, "128, 128, 2, 4, 16, true, {}", 1, False, "", True, 0, 512, "128, 128, 2, 2, 16, false, 0"),
+    _GatherTile("LDS_S", 1, 256, 64, "256, 64, 4, 2, 16, true, {}", 1, False, "", True, 4, 512, "256, 64, 4, 1, 16, false, 0"),
+    _GatherTile("LDS_S", 2, 64, 64, "64, 64, 2, 2, 16, true, {}", 1, False, "", True, 8, 768, "64, 64, 2, 2, 16, false, 0"),
+    _GatherTile("LDS", 3, 256, 128, "256, 128, 4, 2, 16, true, {}", 1, True, "", True, 12, 512),
+    _GatherTile("LDS", 4, 128, 64, "128, 64, 2, 2, 16, true, {}", 1, True, "", True, 16, 768),
+    _GatherTile("LDS", 5, 64, 64, "64, 64, 2, 2, 32, true, {}", 32, True, "", True, 20, 768),
+    _GatherTile("LDS", 6, 128, 64, "128, 64, 2, 2, 32, true, {}", 32, True, "", True, 24, 768),
+    _GatherTile("LDS", 7, 128, 128, "128, 128, 2, 2, 16, true, {}", 1, True, "", True, 28, 768),
+    # 8..11: the LDS-free kernel (off by default, see DIRECT_TILES)
+    _GatherTile("DIRECT", 8, 128, 128, "2, 2, 2, 2, {}", 8, True, "DIRECT_TILES", True, 44, 768),
+    _GatherTile("DIRECT", 9, 256, 64, "4, 1, 2, 2, {}", 8, True, "DIRECT_TILES", True, 48, 768),
+    _GatherTile("DIRECT", 10, 64, 64, "2, 2, 1, 1, {}", 8, True, "DIRECT_TILES", True, 52, 768),
+    _GatherTile("DIRECT", 11, 128, 64, "2, 1, 2, 2, {}", 8, True, "DIRECT_TILES", True, 56, 768),
+    # 12..15: the LDS-DMA family (csrc/conv_gemm_glds.inc); with BN on load: the tiles with 2 or 4 buffers
+    _GatherTile("GLDS", 12, 128, 128, "128, 128, 2, 2, {}, 2, 1, 0", 32, True, "F32_GLDS", True, 104, 512),
+    _GatherTile("GLDS", 13, 128, 64, "128, 64, 2, 2, {}, 3, 1, 0", 32, True, "F32_GLDS", False, 107, 512),
+    _GatherTile("GLDS", 14, 64, 64, "64, 64, 2, 2, {}, 4, 1, 0", 32, True, "F32_GLDS", True, 110, 512),
+    _GatherTile("GLDS", 15, 256, 128, "256, 128, 4, 2, {}, 2, 1, 0", 32, True, "F32_GLDS", True, 113, 256),
+    # 16..19: the same with the fp32 products on the bf16 matrix pipe
+    _GatherTile("EMU", 16, 128, 128, "128, 128, 2, 2, {}, 2, 1, 1", 32, True, "F32_GLDS F32_SPLIT_BF16", False, 130, 512, twin=12),
+    _GatherTile("EMU", 17, 128, 64, "128, 64, 2, 1, {}, 3, 2, 1", 32, True, "F32_GLDS F32_SPLIT_BF16", False, 132, 512, twin=13),
+    _GatherTile("EMU", 18, 64, 64, "64, 64, 2, 1, {}, 4, 2, 1", 32, True, "F32_GLDS F32_SPLIT_BF16", False, 134, 512, twin=14),
+    _GatherTile("EMU", 19, 256, 128, "256, 128, 4, 2, {}, 3, 1, 1", 32, True, "F32_GLDS F32_SPLIT_BF16", False, 136, 256, twin=15),
+)
+_BF16_GATHER_TILES = (
+    _GatherTile("HREG", 0, 128, 128, "128, 128, 2, 2, {}", 1, False, "", True, 60, 768),
+    _GatherTile("HREG", 1, 256, 64, "256, 64, 4, 1, {}", 1, False, "", True, 63, 768),
+    _GatherTile("HREG", 2, 64, 64, "64, 64, 2, 2, {}", 1, False, "", True, 66, 768),
+    _GatherTile("HREG", 3, 256, 128, "256, 128, 4, 2, {}", 1, False, "", True, 69, 512),
+    _GatherTile("HREG", 4, 128, 64, "128, 64, 4, 1, {}", 1, False, "", True, 72, 768),
+    # 5..11: the LDS-DMA family (csrc/conv_gemm_bf16_glds.inc); with BN -> ReLU on load: the two-buffer tiles and the four-buffer
+    # small one.  8 spills registers: not built, never offered
+    _GatherTile("HGLDS", 5, 128, 128, "128, 128, 2, 2, {}, 2", 64, False, "BF16_GLDS", True, 80, 512, kind_bn=94),
+    _GatherTile("HGLDS", 6, 128, 128, "128, 128, 2, 2, {}, 3", 64, False, "BF16_GLDS", False, 82, 256),
+    _GatherTile("HGLDS", 7, 256, 128, "256, 128, 4, 2, {}, 2", 64, False, "BF16_GLDS", True, 84, 256, kind_bn=95),
+    _GatherTile("HNONE", 8, 256, 128, "256, 128, 4, 2, {}, 3", 64, False, "BF16_GLDS", False, 86, None),
+    _GatherTile("HGLDS", 9, 128, 64, "128, 64, 4, 1, {}, 2", 64, False, "BF16_GLDS", True, 88, 768, kind_bn=96),
+    _GatherTile("HGLDS", 10, 128, 64, "128, 64, 4, 1, {}, 3", 64, False, "BF16_GLDS", False, 90, 512),
+    _GatherTile("HGLDS", 11, 64, 64, "64, 64, 2, 2, {}, 4", 64, False, "BF16_GLDS", True, 92, 512, kind_bn=98),
+)
+_GATHER_KERNELS = {"LDS_S": "gather_gemm_kernel", "LDS": "gather_gemm_kernel", "DIRECT": "direct_gemm_kernel",
+                   "GLDS": "gather_gemm_f32_glds_kernel", "EMU": "gather_gemm_f32_glds_kernel",
+                   "HREG": "gather_gemm_bf16_kernel", "HGLDS": "gather_gemm_bf16_glds_kernel"}
+
+# Weight gradients.  route: WgradRoute of the header (W_FOUR: 64 gathered channels x T channels of the small-grid operand).
+#   targs    template arguments of the instantiations with the kinds kind, kind + 1, ..., in the order of the `switch` that ends
+#            decide_wgrad: fp32 W_REG spec 0 / 1 / 2 (scalar_targs: kind 42 / 43), W_FOUR conv / transposed conv; W_MERGE the same;
+#            else plain / BN -> ReLU on x.  The bf16 kinds do not distinguish POW2 (small grid a power of two: the argument after
+#            the BN flag, W_FOUR's last): the name is the power-of-two instantiation's, or carries * for both
+#   targets  blocks in flight the split candidates aim at; one_round: first, the largest split that fits ONE round of
+#            tuner_resident blocks (one block per CU is usually the best -- rb2 of config #2, 24 channel-tile x class blocks:
+#            split 10 = 240 blocks 92 us, split 8 = 192 blocks 105, split 11 = 264 blocks 148)
+_PIXEL_TARGETS = (256, 512, 768, 1024, 1536, 2048, 4096)
+_WgradTile = namedtuple("_WgradTile", "route id T kernel targs vec_only switches bn_form kind tuner_resident targets "
+                                      "one_round scalar_targs twin", defaults=(_PIXEL_TARGETS, False, None, None))
+_F32_WGRAD_TILES = (
+    _WgradTile("W_REG", 0, 128, "wgrad_gemm_kernel", ("128, 128, true, 0", "128, 128, true, 1", "128, 128, true, 2"), False, "", True, 36, 768,
+               scalar_targs="128, 128, false, 0"),
+    _WgradTile("W_REG", 2, 64, "wgrad_gemm_kernel", ("64, 64, true, 0", "64, 64, true, 1", "64, 64, true, 2"), False, "", True, 39, 768,
+               scalar_targs="64, 64, false, 0"),
+    # 5 / 6 = the 128 / 64 tiles on LDS-DMA (csrc/conv_gemm_glds.inc); 7 / 8 = the same with the products on the bf16 matrix pipe
+    _WgradTile("W_GLDS", 5, 128, "wgrad_gemm_f32_glds_kernel", ("128, false, 2, 0", "128, true, 2, 0"), True, "F32_GLDS", True, 116, 768),
+    _WgradTile("W_GLDS", 6, 64, "wgrad_gemm_f32_glds_kernel", ("64, false, 4, 0", "64, true, 2, 0"), True, "F32_GLDS", True, 118, 768),
+    _WgradTile("W_EMU", 7, 128, "wgrad_gemm_f32_glds_kernel", ("128, false, 2, 1",), True, "F32_GLDS F32_SPLIT_BF16", False, 138, 768, twin=5),
+    _WgradTile("W_EMU", 8, 64, "wgrad_gemm_f32_glds_kernel", ("64, false, 4, 1",), True, "F32_GLDS F32_SPLIT_BF16", False, 139, 768, twin=6),
+    # 9 / 10 (k4 s2 p1, small grid of whole 8 x 8 tiles): four taps -- one parity class -- per block, products on the bf16 matrix
+    # pipe (csrc/conv_gemm_glds_parity.inc); without that pipe a plan on them runs on the 64 x 64 register-staged tile
+    _WgradTile("W_FOUR", 9, 64, "wgrad_parity_f32_kernel", ("64, true", "64, false"), True, "F32_GLDS F32_SPLIT_BF16", False, 140, 256,
+               (64, 128, 192, 256, 384, 512, 1024), True, twin=2),
+    _WgradTile("W_FOUR", 10, 128, "wgrad_parity_f32_kernel", ("128, true", "128, false"), True, "F32_GLDS F32_SPLIT_BF16", False, 142, 256,
+               (64, 128, 192, 256, 384, 512, 1024), True, twin=2),
+)
+_BF16_WGRAD_TILES = (
+    _WgradTile("W_REG", 0, 128, "wgrad_gemm_bf16_kernel", ("128, 128, false, true", "128, 128, true, true"), False, "", True, 75, 768),
+    _WgradTile("W_REG", 2, 64, "wgrad_gemm_bf16_kernel", ("64, 64, false, true", "64, 64, true, true"), False, "", True, 77, 768),
+    _WgradTile("W_GLDS", 5, 128, "wgrad_gemm_bf16_glds_kernel", ("128, false, true, 0", "128, true, true, 0"), False, "BF16_GLDS", True, 100, 768),
+    _WgradTile("W_GLDS", 6, 64, "wgrad_gemm_bf16_glds_kernel", ("64, false, true, 0", "64, true, true, 0"), False, "BF16_GLDS", True, 102, 768),
+    # 7 (plain operand): two taps per block on the gathered operand's side when that side has 64 channels
+    _WgradTile("W_MERGE", 7, 128, "wgrad_gemm_bf16_glds_kernel", ("128, false, true, 1", "128, false, true, 2"), False, "BF16_GLDS", False, 120, 768),
+    # 8 / 9 (plain operand, k4 s2 p1, small grid of whole 8 x 8 tiles): four taps -- one parity class -- per block
+    _WgradTile("W_FOUR", 8, 64, "wgrad_parity_bf16_kernel", ("64, *",), False, "BF16_GLDS WGRAD_PARITY", False, 122, 512, (256, 512, 768, 1024, 2048)),
+    _WgradTile("W_FOUR", 9, 128, "wgrad_parity_bf16_kernel", ("128, *",), False, "BF16_GLDS WGRAD_PARITY", False, 123, 256, (256, 512, 768, 1024, 2048)),
+)
+
+
+def _tile_offered(t, g: "Geom", plain_operand: bool) -> bool:
+    """what the tuner asks of any tile, gather or weight gradient: its switches on, a form for the operand, the vector path"""
+    return (all(globals()[s] for s in t.switches.split()) and (t.bn_form or plain_operand)
+            and not (t.vec_only and (g.Cin % 4 or g.Cout % 4)))
 
 
 _forced_plan = None
@@ -309,14 +415,11 @@ def _table_plan(key):
         v = _plan_table.get(plan_key_str(key[:3] + (not key[3],) + key[4:]), False)
     if v is False:
         return False, None
-    if v is not None and not F32_SPLIT_BF16:
-        # the switch is off: a committed plan on the bf16 matrix pipe falls back to the same tile on the fp32 MFMA
-        if key[0] in ("fwd", "dgrad") and v[0] >= 16:
-            v = [v[0] - 4, v[1]]
-        elif key[0] == "wgrad" and v[0] in (7, 8):
-            v = [v[0] - 2, v[1]]
-        elif key[0] == "wgrad" and v[0] in (9, 10):
-            v = [2, v[1]]
+    if v is not None and not F32_SPLIT_BF16 and key[0] in ("fwd", "dgrad", "wgrad"):
+        # the switch is off: a committed plan on the bf16 matrix pipe falls back to the tile's twin on the fp32 MFMA
+        twin = next((t.twin for t in (_F32_WGRAD_TILES if key[0] == "wgrad" else _F32_GATHER_TILES) if t.id == v[0]), None)
+        if twin is not None:
+            v = [twin, v[1]]
     return True, (None if v is None else _Plan(int(v[0]), int(v[1])))
 
 
@@ -380,98 +483,71 @@ def _gather_shape(kind: str, g: Geom):
 WS_COUNTER_BYTES = 64 << 10   # head of the workspace: arrival counters of in-kernel split reductions (header: workspace)
 
 
+def _gather_tile_candidates(tiles, kind: str, g: Geom, ws_bytes: int, plain_operand: bool):
+    """{(tile, split): fraction of the chip the launch occupies} of one family's table, in the order the tuner launches them"""
+    bf16 = tiles is _BF16_GATHER_TILES
+    ws_bytes -= WS_COUNTER_BYTES
+    rows, nphase, taps, ck, cn = _gather_shape(kind, g)
+    iters = taps * (ck // 32 if bf16 else -(-ck // 16))   # (the library's split policy counts 32- / 16-deep K steps)
+    per = rows * nphase * cn * 4
+    cands = {}
+    for t in tiles:
+        if t.kernel == "HNONE" or (t.bm == 256 and rows < 256) or ck % t.k_multiple or not _tile_offered(t, g, plain_operand):
+            continue
+        if t.kernel == "HGLDS" and taps * (ck // t.k_multiple) < 2:
+            continue     # a single 64-deep chunk per tile: nothing to pipeline
+        blocks = -(-rows // t.bm) * -(-cn // t.bn) * nphase
+        cands[(t.id, 1)] = min(1.0, blocks / t.tuner_resident)
+        for s in _SPLITS:
+            if s * 2 <= iters and blocks * s <= 2048 and s * per <= ws_bytes:
+                cands[(t.id, s)] = min(1.0, blocks * s / t.tuner_resident)
+    return cands
+
+
 def _gather_candidates(kind: str, g: Geom, ws_bytes: int, plain_operand: bool = False):
     """plain_operand: no BN -> ReLU on the gathered operand (every LDS-DMA tile applies; with it tiles 12, 14 and 15)"""
     if min(g.Cin, g.Cout) == 1:
         return {}   # image-side edge layers run on the streaming edge kernels: nothing to choose
-    ws_bytes -= WS_COUNTER_BYTES
-    rows, nphase, taps, ck, cn = _gather_shape(kind, g)
-    iters = taps * -(-ck // 16)
-    per = rows * nphase * cn * 4
-    cands = {}   # (tile, split) -> fraction of the chip the launch occupies
-    for tile, (bm, bn) in enumerate(_GATHER_TILES):
-        blocks = -(-rows // bm) * -(-cn // bn) * nphase
-        if bm == 256 and rows < 256:
-            continue
-        if tile >= 3 and (g.Cin % 4 or g.Cout % 4):
-            continue   # vector-path-only tiles
-        if tile in (5, 6) and ck % 32:
-            continue   # 32-deep K chunk
-        if 8 <= tile < 12 and (ck % 8 or not DIRECT_TILES):
-            continue   # LDS-free kernel: 8-deep K steps
-        if tile >= 12 and not (F32_GLDS and ck % 32 == 0 and g.Cin % 4 == 0 and g.Cout % 4 == 0 and (plain_operand or tile != 13)):
-            continue   # LDS-DMA family: 32-deep stages, vector path (with BN on load: the tiles with 2 or 4 buffers)
-        if tile >= 16 and not (F32_SPLIT_BF16 and plain_operand):
-            continue   # products on the bf16 pipe: plain operand forms
-        cap = (256 if tile in (15, 19) else 512) if tile >= 12 else (512 if tile in (0, 1, 3) else 768)   # blocks resident at once
-        cands[(tile, 1)] = min(1.0, blocks / cap)
-        for s in _SPLITS:
-            if s * 2 <= iters and blocks * s <= 2048 and s * per <= ws_bytes:
-                cands[(tile, s)] = min(1.0, blocks * s / cap)
-    return cands
+    return _gather_tile_candidates(_F32_GATHER_TILES, kind, g, ws_bytes, plain_operand)
+
+
+def _gather_candidates_bf16(kind: str, g: Geom, ws_bytes: int, plain_operand: bool = False):
+    """plain_operand: the gathered operand enters the MFMA as it lies in memory (no BN -> ReLU on load): the LDS-DMA tiles apply"""
+    return _gather_tile_candidates(_BF16_GATHER_TILES, kind, g, ws_bytes, plain_operand)
+
+
+def _four_tap(g: Geom) -> bool:
+    """k4 s2 p1 on a small grid of whole 8 x 8 tiles (conv_launch.hpp: four_tap_geometry)"""
+    return ((g.kh, g.kw, g.sh, g.sw, g.ph, g.pw) == (4, 4, 2, 2, 1, 1) and g.Hs % 8 == 0 and g.Ws % 8 == 0
+            and g.Hb == 2 * g.Hs and g.Wb == 2 * g.Ws)
+
+
+def _offer_splits(cands, t, tiles: int, max_split: int):
+    """the tile's targets -> distinct splits of the pixel reduction -> fraction of the chip each occupies"""
+    for s in ([t.tuner_resident // tiles] if t.one_round else []) + [-(-target // tiles) for target in t.targets]:
+        s = max(1, min(s, max_split))
+        if (t.id, s) not in cands:
+            cands[(t.id, s)] = min(1.0, tiles * s / t.tuner_resident)
 
 
 def _wgrad_candidates(g: Geom, bf16: bool = False, plain_operand: bool = False):
     if min(g.Cin, g.Cout) == 1:
         return {}
     ms = g.N * g.Hs * g.Ws
+    cg, csm = (g.Cout, g.Cin) if g.transposed else (g.Cin, g.Cout)   # channels of the gathered / the small-grid operand
     cands = {}
-    # tile 7 (bf16, plain operand): two taps per block on the gathered operand's side when that side has 64 channels
-    if bf16 and BF16_GLDS and plain_operand and g.taps % 2 == 0 and (g.Cout if g.transposed else g.Cin) == 64:
-        tiles = -(-(g.Cin if g.transposed else g.Cout) // 128) * (g.taps // 2)
-        seen = set()
-        for target in (256, 512, 768, 1024, 1536, 2048, 4096):
-            s = max(1, min(-(-target // tiles), -(-ms // 128)))
-            if s not in seen:
-                seen.add(s)
-                cands[(7, s)] = min(1.0, tiles * s / 768)
-    # tile 8 (bf16, plain operand, k4 s2 p1, small grid of whole 8 x 8 tiles): four taps -- one parity class -- per block
-    if (bf16 and BF16_GLDS and WGRAD_PARITY and plain_operand and (g.kh, g.kw, g.sh, g.sw, g.ph, g.pw) == (4, 4, 2, 2, 1, 1)
-            and g.Hs % 8 == 0 and g.Ws % 8 == 0 and g.Hb == 2 * g.Hs and g.Wb == 2 * g.Ws):
-        cg, csm = (g.Cout, g.Cin) if g.transposed else (g.Cin, g.Cout)
-        ntiles = g.N * (g.Hs // 8) * (g.Ws // 8)
-        for tile, cs in ((8, 64), (9, 128)):       # 64 gathered channels x 64 / 128 channels of the small-grid operand
-            if csm % cs:
-                continue
-            tiles = -(-cg // 64) * (csm // cs) * 4
-            seen = set()
-            for target in (256, 512, 768, 1024, 2048):
-                s = max(1, min(-(-target // tiles), ntiles))
-                if s not in seen:
-                    seen.add(s)
-                    cands[(tile, s)] = min(1.0, tiles * s / (256 if cs == 128 else 512))
-    # fp32 tiles 9 / 10 (plain operand, k4 s2 p1, small grid of whole 8 x 8 tiles): four taps per block with the products on the
-    # bf16 matrix pipe (csrc/conv_gemm_glds_parity.inc); 64 gathered channels x 64 / 128 channels of the small-grid operand
-    if (not bf16 and F32_GLDS and F32_SPLIT_BF16 and plain_operand and (g.kh, g.kw, g.sh, g.sw, g.ph, g.pw) == (4, 4, 2, 2, 1, 1)
-            and g.Hs % 8 == 0 and g.Ws % 8 == 0 and g.Hb == 2 * g.Hs and g.Wb == 2 * g.Ws and g.Cin % 4 == 0 and g.Cout % 4 == 0):
-        cg, csm = (g.Cout, g.Cin) if g.transposed else (g.Cin, g.Cout)
-        ntiles = g.N * (g.Hs // 8) * (g.Ws // 8)
-        for tile, cs in ((9, 64), (10, 128)):
-            if csm % cs:
-                continue
-            tiles = -(-cg // 64) * (csm // cs) * 4
-            seen = set()
-            # (one block per CU: the largest split that still fits ONE round of 256 blocks is usually the best -- rb2 of
-            # config #2, 24 channel-tile x class blocks: split 10 = 240 blocks 92 us, split 8 = 192 blocks 105, split 11 = 264 blocks 148)
-            for s in [max(1, min(256 // tiles, ntiles))] + [max(1, min(-(-target // tiles), ntiles)) for target in (64, 128, 192, 256, 384, 512, 1024)]:
-                if s not in seen:
-                    seen.add(s)
-                    cands[(tile, s)] = min(1.0, tiles * s / 256)
-    # tiles 5 / 6 = the 128 / 64 tiles on LDS-DMA (csrc/conv_gemm_glds.inc, conv_gemm_bf16_glds.inc)
-    glds = (BF16_GLDS if bf16 else F32_GLDS and g.Cin % 4 == 0 and g.Cout % 4 == 0)
-    tile_list = ((0, 128), (2, 64), (5, 128), (6, 64)) if glds else ((0, 128), (2, 64))
-    if glds and not bf16 and F32_SPLIT_BF16 and plain_operand:
-        tile_list += ((7, 128), (8, 64))        # fp32 tiles 5 / 6 with the products on the bf16 matrix pipe
-    for tile, tsz in tile_list:
-        if tsz == 128 and (g.Cin <= 64 or g.Cout <= 64):
+    # (the tuner launches candidates in insertion order: the routes with several taps per block first, as ever)
+    for t in sorted(_BF16_WGRAD_TILES if bf16 else _F32_WGRAD_TILES, key=lambda t: t.route not in ("W_MERGE", "W_FOUR")):
+        if not _tile_offered(t, g, plain_operand):
             continue
-        tiles = -(-g.Cin // tsz) * -(-g.Cout // tsz) * g.taps
-        seen = set()
-        for target in (256, 512, 768, 1024, 1536, 2048, 4096):
-            s = max(1, min(-(-target // tiles), -(-ms // 128)))
-            if s not in seen:
-                seen.add(s)
-                cands[(tile, s)] = min(1.0, tiles * s / 768)
+        if t.route == "W_MERGE":
+            if g.taps % 2 == 0 and cg == 64:
+                _offer_splits(cands, t, -(-csm // t.T) * (g.taps // 2), -(-ms // 128))
+        elif t.route == "W_FOUR":
+            if _four_tap(g) and csm % t.T == 0:
+                _offer_splits(cands, t, -(-cg // 64) * (csm // t.T) * 4, g.N * (g.Hs // 8) * (g.Ws // 8))
+        elif t.T == 64 or (g.Cin > 64 and g.Cout > 64):   # (a 128 tile would run half-empty MFMA tiles on <= 64 channels)
+            _offer_splits(cands, t, -(-g.Cin // t.T) * -(-g.Cout // t.T) * g.taps, -(-ms // 128))
     return cands
 
 
@@ -547,39 +623,10 @@ def _tuned_plan(key, cands_fn, launch):
 
 
 BF16 = torch.bfloat16
-_GATHER_TILES_BF16 = ((128, 128), (256, 64), (64, 64), (256, 128), (128, 64),
-                      # 5..11: the LDS-DMA family (csrc/conv_gemm_bf16_glds.inc): operands without a transform on load, K % 64 == 0
-                      (128, 128), (128, 128), (256, 128), (256, 128), (128, 64), (128, 64), (64, 64))
-_GLDS_TILES = {5: 512, 6: 256, 7: 256, 9: 768, 10: 512, 11: 512}     # tile -> blocks resident at once (8 spills: not offered)
-BF16_GLDS = os.environ.get("MOPOE_BF16_GLDS", "1") != "0"      # A/B switch: keep the tuner on the register-staged tiles
-WGRAD_PARITY = os.environ.get("MOPOE_WGRAD_PARITY", "1") != "0"  # A/B switch: wgrad tile 8 (four taps per block) offered
 
 
 def _is16(t):
     return t is not None and t.dtype == BF16
-
-
-def _gather_candidates_bf16(kind: str, g: Geom, ws_bytes: int, plain_operand: bool = False):
-    """plain_operand: the gathered operand enters the MFMA as it lies in memory (no BN -> ReLU on load): the LDS-DMA tiles apply"""
-    ws_bytes -= WS_COUNTER_BYTES
-    rows, nphase, taps, ck, cn = _gather_shape(kind, g)
-    iters = taps * (ck // 32)
-    per = rows * nphase * cn * 4
-    cands = {}
-    for tile, (bm, bn) in enumerate(_GATHER_TILES_BF16):
-        blocks = -(-rows // bm) * -(-cn // bn) * nphase
-        if bm == 256 and rows < 256:
-            continue
-        if tile >= 5 and not (BF16_GLDS and ck % 64 == 0 and tile in _GLDS_TILES and (plain_operand or tile in (5, 7, 9, 11))):
-            continue     # (with BN -> ReLU on load: the two-buffer tiles and the four-buffer small one)
-        if tile >= 5 and taps * (ck // 64) < 2:
-            continue     # a single 64-deep chunk per tile: nothing to pipeline
-        cap = _GLDS_TILES[tile] if tile >= 5 else (512 if tile == 3 else 768)
-        cands[(tile, 1)] = min(1.0, blocks / cap)
-        for sp in _SPLITS:
-            if sp * 2 <= iters and blocks * sp <= 2048 and sp * per <= ws_bytes:
-                cands[(tile, sp)] = min(1.0, blocks * sp / cap)
-    return cands
 
 
 def conv_mix_supported(x, g: Geom) -> bool:
@@ -1324,58 +1371,36 @@ def prof_enable(on: bool):
     _check(lib().mopoe_prof_enable(int(on)))
 
 
-_TILE_TEMPLATES = ("128, 128, 2, 4, 16", "256, 64, 4, 2, 16", "64, 64, 2, 2, 16", "256, 128, 4, 2, 16", "128, 64, 2, 2, 16",
-                   "64, 64, 2, 2, 32", "128, 64, 2, 2, 32", "128, 128, 2, 2, 16")
+def _gather_kinds(t):
+    """[(kind, spec)] of the vector-path instantiations of a gather tile (conv_launch.hpp: kind_of_gather)"""
+    if t.kernel == "HNONE":
+        return []
+    specs = (1, 2, 3) if t.bn_form else (1, 3)
+    if t.kernel in ("LDS_S", "LDS", "DIRECT"):
+        # spec 0 (K no multiple of the chunk) is built where the tuner -- and the decision -- lets such a K reach the tile
+        return [(t.kind + spec, spec) for spec in ((0,) if t.k_multiple == 1 else ()) + specs]
+    if t.kernel in ("GLDS", "HREG"):
+        return [(t.kind + spec - 1, spec) for spec in specs]
+    return [(t.kind_bn if spec == 2 else t.kind + (spec == 3), spec) for spec in specs]     # EMU, HGLDS
 
 
 def _prof_kind_names():
-    """kind index -> the kernel's template name exactly as rocprofv3 prints it (header: MOPOE_PROF_KINDS)"""
+    """kind index -> the kernel's template name as rocprofv3 prints it (header: MOPOE_PROF_KINDS), built from the tile tables;
+    None: no kernel has the kind.  The bf16 weight-gradient kinds do not distinguish POW2 and carry the name of the power-of-two
+    form (or * for both): see the legend of _WgradTile."""
     names = [None] * 144
-    names[140], names[141] = "wgrad_parity_f32_kernel<64, true>", "wgrad_parity_f32_kernel<64, false>"
-    names[142], names[143] = "wgrad_parity_f32_kernel<128, true>", "wgrad_parity_f32_kernel<128, false>"
-    names[138], names[139] = "wgrad_gemm_f32_glds_kernel<128, false, 2, 1>", "wgrad_gemm_f32_glds_kernel<64, false, 4, 1>"
-    for i, tt in enumerate(("128, 128, 2, 2, {}, 2, 1, 1", "128, 64, 2, 1, {}, 3, 2, 1", "64, 64, 2, 1, {}, 4, 2, 1", "256, 128, 4, 2, {}, 3, 1, 1")):
-        for k, spec in enumerate((1, 3)):
-            names[130 + 2 * i + k] = f"gather_gemm_f32_glds_kernel<{tt.format(spec)}>"
-    names[127], names[128], names[129] = "pw_front_fwd_f32_kernel<false>", "pw_front_fwd_f32_kernel<true>", "pw_front_bwd_f32_kernel"
-    names[124], names[125], names[126] = "pw_front_fwd_bf16_kernel<64, false>", "pw_front_fwd_bf16_kernel<64, true>", "pw_front_bwd_bf16_kernel<64>"
-    names[122], names[123] = "wgrad_parity_bf16_kernel<64, *>", "wgrad_parity_bf16_kernel<128, *>"
-    for m in (1, 2):
-        names[120 + m - 1] = f"wgrad_gemm_bf16_glds_kernel<128, false, true, {m}>"
-    for i, (tt, st) in enumerate((("128", (2, 2)), ("64", (4, 2)))):
-        for xf in (0, 1):
-            names[116 + 2 * i + xf] = f"wgrad_gemm_f32_glds_kernel<{tt}, {'true' if xf else 'false'}, {st[xf]}, 0>"
-    for i, tt in enumerate(("128, 128, 2, 2, {}, 2, 1, 0", "128, 64, 2, 2, {}, 3, 1, 0", "64, 64, 2, 2, {}, 4, 1, 0", "256, 128, 4, 2, {}, 2, 1, 0")):
-        for spec in (1, 2, 3):
-            names[104 + 3 * i + spec - 1] = f"gather_gemm_f32_glds_kernel<{tt.format(spec)}>"
-    for i, tt in enumerate(("128", "64")):
-        for xf in (0, 1):
-            names[100 + 2 * i + xf] = f"wgrad_gemm_bf16_glds_kernel<{tt}, {'true' if xf else 'false'}, true, 0>"
-    for i, tt in enumerate(("128, 128, 2, 2, 2, 2", "256, 128, 4, 2, 2, 2", "128, 64, 4, 1, 2, 2")):
-        names[94 + i] = f"gather_gemm_bf16_glds_kernel<{tt}>"
-    names[98] = "gather_gemm_bf16_glds_kernel<64, 64, 2, 2, 2, 4>"
-    for i, tt in enumerate(("128, 128, 2, 2, {}, 2", "128, 128, 2, 2, {}, 3", "256, 128, 4, 2, {}, 2", "256, 128, 4, 2, {}, 3",
-                            "128, 64, 4, 1, {}, 2", "128, 64, 4, 1, {}, 3", "64, 64, 2, 2, {}, 4")):
-        for k, spec in enumerate((1, 3)):
-            names[80 + 2 * i + k] = f"gather_gemm_bf16_glds_kernel<{tt.format(spec)}>"
-    for tile, tt in enumerate(("128, 128, 2, 2", "256, 64, 4, 1", "64, 64, 2, 2", "256, 128, 4, 2", "128, 64, 4, 1")):
-        for spec in (1, 2, 3):
-            names[60 + tile * 3 + spec - 1] = f"gather_gemm_bf16_kernel<{tt}, {spec}>"
-    for i, tt in enumerate(("128, 128", "64, 64")):
-        for xf in (0, 1):
-            names[75 + 2 * i + xf] = f"wgrad_gemm_bf16_kernel<{tt}, {'true' if xf else 'false'}, true>"
-    for tile, tt in enumerate(_TILE_TEMPLATES):
-        for spec in range(4):
-            names[tile * 4 + spec] = f"gather_gemm_kernel<{tt}, true, {spec}>"
-    for i, tt in enumerate(("128, 128, 2, 2, 16", "256, 64, 4, 1, 16", "64, 64, 2, 2, 16")):
-        names[32 + i] = f"gather_gemm_kernel<{tt}, false, 0>"
-    for i, tt in enumerate(("128, 128", "64, 64")):
-        for spec in range(3):
-            names[36 + 3 * i + spec] = f"wgrad_gemm_kernel<{tt}, true, {spec}>"
-        names[42 + i] = f"wgrad_gemm_kernel<{tt}, false, 0>"
-    for i, tt in enumerate(("2, 2, 2, 2", "4, 1, 2, 2", "2, 2, 1, 1", "2, 1, 2, 2")):
-        for spec in range(1, 4):
-            names[44 + 4 * i + spec] = f"direct_gemm_kernel<{tt}, {spec}>"
+    for t in _F32_GATHER_TILES + _BF16_GATHER_TILES:
+        for kind, spec in _gather_kinds(t):
+            names[kind] = f"{_GATHER_KERNELS[t.kernel]}<{t.targs.format(spec)}>"
+        if t.scalar_targs:
+            names[32 + t.id] = f"{_GATHER_KERNELS[t.kernel]}<{t.scalar_targs}>"
+    for t in _F32_WGRAD_TILES + _BF16_WGRAD_TILES:
+        for i, targs in enumerate(t.targs):
+            names[t.kind + i] = f"{t.kernel}<{targs}>"
+        if t.scalar_targs:
+            names[42 + (t.T != 128)] = f"{t.kernel}<{t.scalar_targs}>"
+    names[124:130] = ("pw_front_fwd_bf16_kernel<64, false>", "pw_front_fwd_bf16_kernel<64, true>", "pw_front_bwd_bf16_kernel<64>",
+                      "pw_front_fwd_f32_kernel<false>", "pw_front_fwd_f32_kernel<true>", "pw_front_bwd_f32_kernel")   # csrc/pointwise.hip
     return names
 
 

@@ -29,6 +29,38 @@ def test_library_exports_every_declared_symbol():
     assert lib.mopoe_abi_version() == ops.ABI_VERSION
 
 
+def test_profiling_names_are_the_kernels_of_the_built_library():
+    """ops.PROF_KINDS (built from the tile tables of mimic_amd/ops.py) against the dynamic symbols of libmopoe_hip.so: every name
+    is a kernel that was instantiated (* = any one argument), and every conv / block-front kernel has a name -- except the
+    POW2 = false twins of the bf16 weight-gradient kernels, which share a kind with their named POW2 = true form."""
+    import fnmatch
+    import shutil
+    import subprocess
+    from mimic_amd import ops
+    if not os.path.exists(ops.LIB_PATH) or not shutil.which("nm"):
+        pytest.skip("needs the built library and nm")
+    lines = subprocess.check_output(["nm", "-DC", ops.LIB_PATH], text=True).splitlines()
+    kernels = {re.sub(r"^(void )?mopoe::", "", ln.split(None, 2)[2]).rsplit("(", 1)[0]
+               for ln in lines if "_kernel" in ln and "__device_stub__" not in ln}
+    names = [n for n in ops.PROF_KINDS if n is not None]
+    assert len(kernels) > 100 and len(set(names)) == len(names)
+    dead = [n for n in names if not fnmatch.filter(kernels, n)]
+    assert not dead, f"PROF_KINDS names kernels the library does not have: {dead}"
+    # a bf16 weight-gradient kernel with POW2 = false runs under the kind of its twin: the same arguments with that one true
+    pow2_at = {"wgrad_gemm_bf16_kernel": 3, "wgrad_gemm_bf16_glds_kernel": 2}
+    def pow2_twin(k):
+        base, args = k.split("<")[0], k[k.index("<") + 1:-1].split(", ") if "<" in k else []
+        if base not in pow2_at or args[pow2_at[base]] != "false":
+            return None
+        args[pow2_at[base]] = "true"
+        return f"{base}<{', '.join(args)}>"
+    families = ("gather_gemm", "direct_gemm", "wgrad_gemm", "wgrad_parity", "pw_front")
+    unnamed = [k for k in sorted(kernels) if k.startswith(families) and not any(fnmatch.fnmatchcase(k, n) for n in names)]
+    twins = [k for k in unnamed if pow2_twin(k) in names]
+    assert unnamed == twins, f"kernels without a profiling name: {sorted(set(unnamed) - set(twins))}"
+    assert twins      # (ten today: every bf16 weight-gradient kind but the two with * has one)
+
+
 def test_no_cpu_fallback():
     from mimic_amd import ops
     with pytest.raises(ops.MopoeHipError):

@@ -8,7 +8,8 @@ launched.
     fusions of each op, a second workspace size (counters + three output slabs), on geometries chosen for the branches (direct
     tiles, scalar path, K chunks that do not divide, the 64-column remainder, fewer than 64 rows, more output tiles than arrival
     counters, four-tap and two-tap weight gradients);
-  * every accepted decision's profiling kind is one ops.PROF_KINDS names.
+  * every accepted decision's profiling kind is one ops.PROF_KINDS names, with the kernel of the decided tile and its block;
+  * the tile tables of mimic_amd/ops.py (tuner candidates, kernel names) agree with the header's on every field they share.
 
 Edge-kernel routing happens in the extern "C" entry points in front of the decision and is not part of it: those cases are
 skipped, and the test holds the skipped set to exactly them.
@@ -30,6 +31,10 @@ SHIM_SRC = os.path.join(HERE, "tools", "conv_launch_shim.cpp")
 WGRAD_ROUTES = ("reg", "glds", "emu", "glds", "four_tap")     # WgradRoute -> the mirror's name (two taps per block: an LDS-DMA form)
 GATHER_OUT = ("vec", "tile", "emu", "spec", "nsplit", "reduce", "gx", "nNt", "nphase", "bm", "bn", "bk", "rows", "rows_total", "kind", "slab_offset")
 WGRAD_OUT = ("route", "T", "big", "merge", "vec", "split", "chunk", "atomic", "fast", "spec", "nI", "nJ", "gx", "gy", "gz", "kind")
+GATHER_TILE = ("kernel", "id", "bm", "bn", "threads", "bk", "stages", "bn_form", "in_kernel", "kind", "kind_bn")
+WGRAD_TILE = ("route", "id", "T", "kp", "kind")
+GATHER_KERNELS = ("LDS_S", "LDS", "DIRECT", "GLDS", "EMU", "HREG", "HGLDS", "HNONE")     # enum GatherKernel, without G_
+WGRAD_ROUTE_NAMES = ("W_REG", "W_GLDS", "W_EMU", "W_MERGE", "W_FOUR")                     # enum WgradRoute
 
 
 @pytest.fixture(scope="session")
@@ -42,6 +47,15 @@ def shim(tmp_path_factory):
     lib.shim_ws_counter_bytes.restype = lib.shim_ws_recommended.restype = ctypes.c_longlong
     lib.shim_gather.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
     lib.shim_wgrad.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+    lib.shim_gather_tile.argtypes = lib.shim_wgrad_tile.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    # the library's tile tables: {(family, "gather" | "wgrad"): [row as a dict]}
+    lib.tiles = {}
+    for fam, (grp, door, fields) in itertools.product((0, 1), (("gather", lib.shim_gather_tile, GATHER_TILE), ("wgrad", lib.shim_wgrad_tile, WGRAD_TILE))):
+        buf, rows = (ctypes.c_int * len(fields))(), []
+        while door(fam, len(rows), buf) == 0:
+            rows.append(dict(zip(fields, buf)))
+        assert door(fam, -1, buf) != 0 and door(fam, len(rows) + 1, buf) != 0
+        lib.tiles[(fam, grp)] = rows
     return lib
 
 
@@ -64,7 +78,7 @@ def decide(lib, op, g, bn=False, mask=0, relu_bn=0, mix=False, out_f32=False, pl
         if rc:
             assert rc == -1, rc
             raise PC.PlanRefused(_MSG.value.decode())
-        d = dict(zip(WGRAD_OUT, _OUT))
+        d = dict(zip(WGRAD_OUT, _OUT), fam=fam, group="wgrad")
         d.update(route=WGRAD_ROUTES[d["route"]], route_id=d["route"], vec=bool(d["vec"]), tile=tile,
                  fast=bool(d["fast"]) or (fam == 1 and d["route"] == 4))     # (the mirror's bf16 four-tap form carries fast = True)
         return d
@@ -76,7 +90,7 @@ def decide(lib, op, g, bn=False, mask=0, relu_bn=0, mix=False, out_f32=False, pl
     if rc:
         assert rc == -1, rc
         raise PC.PlanRefused(_MSG.value.decode())
-    d = dict(zip(GATHER_OUT, _OUT))
+    d = dict(zip(GATHER_OUT, _OUT), fam=fam, group="gather")
     d.update(route="gemm", vec=bool(d["vec"]), emu=bool(d["emu"]), fast=d["spec"] != 0, multi_m=PC._cdiv(d["rows"], d["bm"]) > 1)
     return d
 
@@ -88,8 +102,72 @@ def differences(mirror, lib):
     return {k: (mirror[k], lib[k]) for k in COMPARED if k in mirror and mirror[k] != lib[k]}
 
 
-def check_kind(d):
-    assert 0 <= d["kind"] < len(ops.PROF_KINDS) and ops.PROF_KINDS[d["kind"]] is not None, d
+def _template_ints(name):
+    return [int(x) for x in name[name.index("<") + 1:-1].split(", ") if x.isdigit()]
+
+
+def _block_of(kernel, args):
+    """(bm, bn) a gather kernel's template arguments stand for: BM, BN lead them, except direct_gemm_kernel<WGM, WGN, MI, NI, spec>
+    (32 x 32 MFMA tiles: MI x NI per wave)"""
+    return (32 * args[0] * args[2], 32 * args[1] * args[3]) if kernel == "DIRECT" else (args[0], args[1])
+
+
+def check_kind(lib, d):
+    """the decision's kind has a name in ops.PROF_KINDS, and it is the kernel of the decided tile with the decided block"""
+    name = ops.PROF_KINDS[d["kind"]] if 0 <= d["kind"] < len(ops.PROF_KINDS) else None
+    assert name is not None, d
+    if d["group"] == "gather":
+        row = lib.tiles[(d["fam"], "gather")][d["tile"] + (4 if d["emu"] else 0)]
+        kernel = GATHER_KERNELS[row["kernel"]]
+        assert (row["bm"], row["bn"]) == (d["bm"], d["bn"]) and name.startswith(ops._GATHER_KERNELS[kernel] + "<"), (name, d)
+        assert _block_of(kernel, _template_ints(name)) == (d["bm"], d["bn"]), (name, d)
+        assert ("false" in name) == (d["fam"] == 0 and not d["vec"]), (name, d)      # (the scalar path's forms, and no other, say so)
+    else:
+        mine = [t for t in (ops._BF16_WGRAD_TILES if d["fam"] else ops._F32_WGRAD_TILES)
+                if (t.route, t.T) == (WGRAD_ROUTE_NAMES[d["route_id"]], d["T"])]
+        assert len(mine) == 1 and name.startswith(mine[0].kernel + "<") and _template_ints(name)[0] == d["T"], (name, d)
+
+
+# ---- the tuner's tile tables (mimic_amd/ops.py) against the library's ----------------------------------------------------------------
+def test_the_tuners_tile_tables_restate_the_librarys(shim):
+    for fam, mine in ((0, ops._F32_GATHER_TILES), (1, ops._BF16_GATHER_TILES)):
+        theirs = shim.tiles[(fam, "gather")]
+        assert len(mine) == len(theirs) and [t.id for t in mine] == [r["id"] for r in theirs] == list(range(len(mine)))
+        for t, r in zip(mine, theirs):
+            assert (GATHER_KERNELS.index(t.kernel), t.bm, t.bn, int(t.bn_form), t.kind, t.kind_bn or 0) == \
+                   (r["kernel"], r["bm"], r["bn"], r["bn_form"], r["kind"], r["kind_bn"]), (t, r)
+            assert t.k_multiple in (1, r["bk"]), (t, r)      # where the tuner asks for a K multiple it is the tile's K chunk
+            assert (t.scalar_targs is not None) == (t.kernel == "LDS_S") and (t.kernel == "LDS_S" or fam == 1) != t.vec_only, t
+            # the template arguments say what the row says: block, waves and, where they are arguments, K chunk and LDS buffers
+            a = _template_ints(f"<{t.targs.format(1)}>")
+            waves = a[0] * a[1] if t.kernel == "DIRECT" else a[2] * a[3] * (a[6] if t.kernel in ("GLDS", "EMU") else 1)
+            assert _block_of(t.kernel, a) == (t.bm, t.bn) and 64 * waves == r["threads"], (t, r)
+            if t.kernel in ("LDS_S", "LDS"):
+                assert a[4] == r["bk"] and (not t.scalar_targs or _template_ints(f"<{t.scalar_targs}>")[:2] == [t.bm, t.bn]), (t, r)
+            if t.kernel in ("GLDS", "EMU", "HGLDS"):
+                assert a[5] == r["stages"] and (t.kernel == "HGLDS" or a[7] == (t.kernel == "EMU")), (t, r)
+            # a twin is the same block on the fp32 MFMA
+            if t.twin is not None:
+                assert t.kernel == "EMU" and (mine[t.twin].kernel, mine[t.twin].bm, mine[t.twin].bn) == ("GLDS", t.bm, t.bn), t
+            assert (t.twin is not None) == (t.kernel == "EMU"), t
+    for fam, mine in ((0, ops._F32_WGRAD_TILES), (1, ops._BF16_WGRAD_TILES)):
+        theirs = shim.tiles[(fam, "wgrad")]
+        assert len(mine) == len(theirs)
+        for t, r in zip(mine, theirs):
+            assert (WGRAD_ROUTE_NAMES.index(t.route), t.id, t.T, t.kind) == (r["route"], r["id"], r["T"], r["kind"]), (t, r)
+            assert all(_template_ints(f"<{a}>")[0] == t.T for a in t.targs + ((t.scalar_targs,) if t.scalar_targs else ())), t
+            # a twin runs without the bf16 matrix pipe on the same block -- of a four-tap tile (64 gathered channels x T): on
+            # the 64 x 64 register-staged tile, whatever T
+            assert (t.twin is not None) == (fam == 0 and t.route in ("W_EMU", "W_FOUR")), t
+            if t.twin is not None:
+                twin = [u for u in mine if u.id == t.twin]
+                assert len(twin) == 1 and (twin[0].route, twin[0].T) == (("W_REG", 64) if t.route == "W_FOUR" else ("W_GLDS", t.T)), t
+    # no kind is named twice: every name of PROF_KINDS comes from one row and one instantiation
+    kinds = [k for t in ops._F32_GATHER_TILES + ops._BF16_GATHER_TILES for k, _ in ops._gather_kinds(t)] + \
+            [32 + t.id for t in ops._F32_GATHER_TILES if t.scalar_targs] + \
+            [t.kind + i for t in ops._F32_WGRAD_TILES + ops._BF16_WGRAD_TILES for i in range(len(t.targs))] + [42, 43] + list(range(124, 130))
+    assert len(kinds) == len(set(kinds)) and set(kinds) == {i for i, n in enumerate(ops.PROF_KINDS) if n is not None}
+    assert len(ops.PROF_KINDS) == 144      # include/mopoe_hip.h: MOPOE_PROF_KINDS
 
 
 # ---- the committed plan table ------------------------------------------------------------------------------------------------
@@ -112,7 +190,7 @@ def test_every_case_of_the_plan_table_decides_as_the_mirror_says(shim):
                 edge.append((c.id, g.N))
                 continue
             got = _case_decision(shim, c, g)
-            check_kind(got)
+            check_kind(shim, got)
             diff = differences(want, got)
             if diff:
                 bad.append((c.id, g.N, diff))
@@ -202,7 +280,7 @@ def test_the_sweep_decides_as_the_mirror_says_and_reaches_every_branch(shim):
         if (want is None) != (got is None):
             bad.append((op, g, flags, plan, ws, "mirror " + ("refuses" if want is None else "accepts")))
         elif got is not None:
-            check_kind(got)
+            check_kind(shim, got)
             diff = differences(want, got)
             if diff:
                 bad.append((op, g, flags, plan, ws, diff))

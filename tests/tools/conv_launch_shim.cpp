@@ -17,6 +17,25 @@ static mopoe_conv_geom geom(const int* v) {   // N, Hs, Ws, Hb, Wb, Cin, Cout, k
 extern "C" long long shim_ws_counter_bytes(void) { return (long long)WS_COUNTER_BYTES; }
 extern "C" long long shim_ws_recommended(void) { return (long long)WS_RECOMMENDED; }
 
+// row i of a family's tile table (non-zero past its end) -> kernel, id, bm, bn, threads, bk, stages, bn_form, in_kernel, kind, kind_bn
+extern "C" int shim_gather_tile(int family, int i, int* out) {
+  if (i < 0 || i >= (family ? BF16_NTILES : F32_NTILES)) return 1;
+  const GatherTile& t = (family ? BF16_GATHER_TILES : F32_GATHER_TILES)[i];
+  const int r[11] = {t.kernel, t.id, t.bm, t.bn, t.threads(), t.bk, t.stages, t.bn_form, t.in_kernel, t.kind, t.kind_bn};
+  memcpy(out, r, sizeof r);
+  return 0;
+}
+
+// ... of its weight-gradient table -> route, id, T, kp, kind
+extern "C" int shim_wgrad_tile(int family, int i, int* out) {
+  const int n = (int)(family ? sizeof(BF16_WGRAD_TILES) : sizeof(F32_WGRAD_TILES)) / (int)sizeof(WgradTile);
+  if (i < 0 || i >= n) return 1;
+  const WgradTile& t = (family ? BF16_WGRAD_TILES : F32_WGRAD_TILES)[i];
+  const int r[5] = {t.route, t.id, t.T, t.kp, t.kind};
+  memcpy(out, r, sizeof r);
+  return 0;
+}
+
 // in: dest_on_small, Ck, Cn, w_nk, bn_on_load, mask kind, relu_bn mode, mix, out_f32, aligned, plan tile, plan split,
 //     !MOPOE_NO_XCD_REMAP, !MOPOE_BF16_NO_GLDS (every tensor the flags call for is present, its BatchNorm has the right C)
 // out: vec, tile, emu, spec, nsplit, reduce, gx, nNt, nphase, bm, bn, bk, rows_per_phase, rows_total, kind, slab offset
