@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPOE_ABI_VERSION 23
+#define MOPOE_ABI_VERSION 24
 
 /* error codes */
 #define MOPOE_OK 0

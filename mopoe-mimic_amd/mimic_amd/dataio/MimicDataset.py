@@ -369,12 +369,22 @@ class DeviceResidentMimic:
 
     Sharding and shuffling follow DistributedSampler (dataio/utils.py:121): a seeded permutation per epoch, padded by
     wrap-around to a multiple of world_size, rank r takes elements r, r + W, ...; `drop_last` is False like the
-    reference's DataLoader (the last batch may be short: the train loop runs it eagerly)."""
+    reference's DataLoader (the last batch may be short: the train loop runs it eagerly).
+
+    `weights` (float64 [n], dataio.utils.label_weights) selects --weighted_sampler: the rows of an epoch are drawn WITH
+    replacement in proportion to their weight, on the device.  Only the weights' prefix sum is kept there; `__iter__`
+    launches one ops.batch_draw for the rank's ceil(n / world_size) draws of the epoch -- a function of (seed, epoch, rank,
+    draw number), so `__len__` is unchanged and ranks draw independently -- and yields one ops.batch_assemble result per
+    slice of that index tensor: no host read and no sync.  There is no CPU form of it, as everywhere in ops."""
 
     def __init__(self, dataset, device, batch_size: int, shuffle: bool = True, rank: int = 0, world_size: int = 1,
-                 seed: int = 0):
+                 seed: int = 0, weights=None):
         """dataset: a MimicSplit, or a Mimic (its `files`)"""
         from .utils import resize_u8
+        if weights is not None and torch.device(device).type != "cuda":
+            from ..ops import MopoeHipError
+            raise MopoeHipError("DeviceResidentMimic(weights=...) draws and assembles its batches with HIP kernels: it needs a "
+                                "GPU device (no CPU fallback); on the CPU use dataio.utils.get_data_loaders(weighted_sampler=True)")
         files = dataset.files if isinstance(dataset, Mimic) else dataset
         args = dataset.args if isinstance(dataset, Mimic) else files.args      # (a view may ask for another image size)
         self.device, self.batch_size, self.shuffle = torch.device(device), int(batch_size), shuffle
@@ -386,8 +396,17 @@ class DeviceResidentMimic:
         # word: token ids [n, L] int32; char: alphabet positions [n, L] uint8, expanded to one-hot rows on the device
         self.num_features = None if files.sentences is not None else len(files.args.alphabet)
         self.text = files.text_ids().to(self.device)
-        self.labels = files.label_matrix.to(self.device)
+        # (row-major: the label frame's values come column-major out of pandas, and the batch kernel reads rows)
+        self.labels = files.label_matrix.to(self.device).contiguous()
         self.n = len(files)
+        self.cdf = None
+        if weights is not None:
+            weights = torch.as_tensor(weights)
+            if weights.dtype != torch.float64 or tuple(weights.shape) != (self.n,):
+                raise ValueError(f"weights: a float64 vector with one entry per row [{self.n}], got {weights.dtype} "
+                                 f"{tuple(weights.shape)}")
+            # the inclusive prefix sum, summed once on the host in fp64: what the draw kernel searches
+            self.cdf = torch.cumsum(weights.cpu(), 0).to(self.device)
 
     def set_epoch(self, epoch: int):
         self.epoch = epoch
@@ -406,7 +425,19 @@ class DeviceResidentMimic:
         per_rank = -(-self.n // self.world_size)
         return -(-per_rank // self.batch_size)
 
+    def _iter_weighted(self):
+        from .. import ops
+        count = -(-self.n // self.world_size)
+        order = ops.batch_draw(self.cdf, self.seed, self.epoch, self.rank, 0, count)
+        for s in range(0, count, self.batch_size):
+            pa, lat, text, labels = ops.batch_assemble(self.pa, self.lat, self.text, self.labels, order[s:s + self.batch_size],
+                                                       self.num_features)
+            yield {"PA": pa, "Lateral": lat, "text": text}, labels
+
     def __iter__(self):
+        if self.cdf is not None:
+            yield from self._iter_weighted()
+            return
         order = torch.tensor(self._indices(), dtype=torch.long, device=self.device)
         for s in range(0, order.numel(), self.batch_size):
             sel = order[s:s + self.batch_size]

@@ -71,15 +71,57 @@ def get_str_labels(binary_labels):
     return ["Finding"] if binary_labels else ["Lung Opacity", "Pleural Effusion", "Support Devices"]
 
 
-def get_data_loaders(args, dataset, which_set: str = "train", weighted_sampler: bool = False, nbr_samples_4_sampler: int = -1):
-    if weighted_sampler:
-        raise NotImplementedError("label-weighted sampling is used by the classifier training only (outside the hot path)")
-    workers = int(getattr(args, "dataloader_workers", 0))
-    if getattr(args, "distributed", False):
-        sampler = torch.utils.data.distributed.DistributedSampler(dataset)
-        workers = workers // max(1, int(getattr(args, "world_size", 1)))
+def label_weights(label_frame, binary_labels) -> torch.Tensor:
+    """Per-row sampling weights of --weighted_sampler, float64 [n]: the reference's calculateWeights (dataio/utils.py:81-94)
+    without its row loop.  Three labels: sum over the labels of row[l] / count[l], plus 1 / (N - count0 - count1 - count2) for
+    a row without any finding; binary: 1 / count for a 1-row, 1 / (N - count) for a 0-row.  The terms are added in the
+    reference's order, ((t0 + t1) + t2) + t_none, so the sums are the reference's bit for bit; a label no row carries
+    contributes 0.
+
+    The three-label "no finding" denominator is NOT the number of such rows (a row with two findings is subtracted twice):
+    it can be zero or negative, and the sampler would be handed an infinite or a negative probability.  Such a table -- and
+    any other that yields a weight that is not finite and positive -- is refused here with a ValueError."""
+    cols = list(label_frame.columns)[:1 if binary_labels else 3]
+    if len(cols) < (1 if binary_labels else 3):
+        raise ValueError(f"label_weights: the label table has columns {list(label_frame.columns)}, "
+                         f"{'one is' if binary_labels else 'three are'} needed")
+    v = label_frame[cols].to_numpy(dtype=np.float64)
+    n = v.shape[0]
+    counts = (v == 1).sum(axis=0).astype(np.int64)
+    if binary_labels:
+        denom = n - int(counts[0])
+        none = v[:, 0] == 0
+        w = (v[:, 0] == 1) * (1.0 / counts[0] if counts[0] > 0 else 0.0)
     else:
-        sampler = None
+        denom = n - int(counts.sum())
+        none = (v == 0).all(axis=1)
+        terms = [v[:, l] / counts[l] if counts[l] > 0 else np.zeros(n) for l in range(3)]
+        w = (terms[0] + terms[1]) + terms[2]
+    what = f"label counts {dict(zip(cols, counts.tolist()))}, N = {n}"
+    if none.any():
+        if denom <= 0:
+            raise ValueError(f"label_weights: {int(none.sum())} rows have no finding but their weight's denominator is {denom} "
+                             f"({what}): the reference's formula has no valid sampling weight for this label table")
+        w = w + none * (1.0 / denom)
+    if not (np.isfinite(w).all() and (w > 0).all()):
+        raise ValueError(f"label_weights: {int((~(np.isfinite(w) & (w > 0))).sum())} rows get a weight that is not finite and "
+                         f"positive ({what})")
+    return torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64))
+
+
+def get_data_loaders(args, dataset, which_set: str = "train", weighted_sampler: bool = False, nbr_samples_4_sampler: int = -1):
+    """nbr_samples_4_sampler: how many rows the weighted sampler draws per epoch (-1: as many as the dataset has)"""
+    workers = int(getattr(args, "dataloader_workers", 0))
+    sampler = None
+    if getattr(args, "distributed", False):
+        workers = workers // max(1, int(getattr(args, "world_size", 1)))
+    if which_set == "train" and weighted_sampler:
+        # (as in the reference, dataio/utils.py:126-133, this sampler takes the distributed sampler's place)
+        weights = label_weights(dataset.labels, getattr(args, "binary_labels", False))
+        num = len(weights) if nbr_samples_4_sampler == -1 else int(nbr_samples_4_sampler)
+        sampler = torch.utils.data.sampler.WeightedRandomSampler(weights, num, replacement=True)
+    elif getattr(args, "distributed", False):
+        sampler = torch.utils.data.distributed.DistributedSampler(dataset)
     d_loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=(sampler is None), num_workers=workers,
                           sampler=sampler, pin_memory=torch.cuda.is_available())
     assert len(d_loader), f"length of the dataloader needs to be at least 1, it is {len(d_loader)}"
@@ -88,8 +130,9 @@ def get_data_loaders(args, dataset, which_set: str = "train", weighted_sampler: 
 
 def samplers_set_epoch(args, train_sampler, test_sampler, epoch: int) -> None:
     if getattr(args, "distributed", False):
-        train_sampler.set_epoch(epoch)
-        test_sampler.set_epoch(epoch)
+        for sampler in (train_sampler, test_sampler):
+            if hasattr(sampler, "set_epoch"):      # (a WeightedRandomSampler has no epoch: it draws from the global generator)
+                sampler.set_epoch(epoch)
 
 
 def shard_for_rank(n: int, rank: int, world_size: int, perm=None):

@@ -21,7 +21,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOPOE_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libmopoe_hip.so")  # env override: A/B builds
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 RES_A, RES_B = 2.0, 0.3
 BN_EPS = 1e-5
@@ -1362,6 +1362,49 @@ def embedding_bwd(ids, gout, vocab, padding_idx=0):
     fn = lib().mopoe_embedding_bwd_bf16 if _is16(gout) else lib().mopoe_embedding_bwd
     _check(fn(_p(ids), _p(gout), _p(dtable), C.c_int64(ids.numel()), vocab, gout.shape[-1], padding_idx, _stream()))
     return dtable
+
+
+# ----------------------------------------------------------------------------------------------
+# input pipeline of --weighted_sampler (include/mopoe_hip_data.h, csrc/batch.hip)
+# ----------------------------------------------------------------------------------------------
+def batch_draw(cdf, seed: int, epoch: int, rank: int, first: int, count: int):
+    """cdf: double [n], the inclusive prefix sum of the rows' weights -> int64 [count]: the rows that draws first .. first +
+    count - 1 of (seed, epoch, rank) select, with replacement (Philox4x32-10 per draw, binary search in cdf)"""
+    _dev(cdf)
+    if cdf.dim() != 1 or cdf.numel() < 1 or cdf.dtype != torch.float64:
+        raise MopoeHipError("batch_draw: cdf is a float64 vector [n] with n >= 1")
+    seed, epoch, rank, first, count = int(seed), int(epoch), int(rank), int(first), int(count)
+    if first < 0 or count < 0 or not (0 <= epoch < 1 << 32) or not (0 <= rank < 1 << 32):
+        raise MopoeHipError("batch_draw: first >= 0, count >= 0, epoch and rank in [0, 2^32)")
+    out = torch.empty(count, dtype=torch.int64, device=cdf.device)
+    _check(lib().mopoe_batch_draw(_p(cdf), C.c_int64(cdf.numel()), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint32(epoch),
+                                  C.c_uint32(rank), C.c_int64(first), C.c_int64(count), _p(out), _stream()))
+    return out
+
+
+def batch_assemble(pa, lat, text, labels, sel, num_features: Optional[int] = None):
+    """pa, lat: uint8 [n,S,S]; text: int32 [n,L] token ids (num_features None) or uint8 [n,L] alphabet positions; labels: float
+    [n,n_labels]; sel: int64 [B] row numbers (clamped into [0, n)) -> (PA [B,1,S,S], Lateral [B,1,S,S], text [B,L] or one-hot
+    [B,L,num_features], labels [B,n_labels]), all float32: images as u8 / 255 with a correctly rounded division"""
+    _dev(pa, lat, text, labels, sel)
+    char = num_features is not None
+    if (pa.dim() != 3 or pa.shape[1] != pa.shape[2] or lat.shape != pa.shape or pa.dtype != torch.uint8 or lat.dtype != torch.uint8
+            or text.dim() != 2 or labels.dim() != 2 or text.shape[0] != pa.shape[0] or labels.shape[0] != pa.shape[0]
+            or text.dtype != (torch.uint8 if char else torch.int32) or labels.dtype != torch.float32
+            or sel.dim() != 1 or sel.dtype != torch.int64 or sel.numel() < 1 or pa.shape[0] < 1
+            or (char and int(num_features) < 1) or any(t.device != pa.device for t in (lat, text, labels, sel))):
+        raise MopoeHipError("batch_assemble: pa / lat uint8 [n,S,S], text int32 [n,L] (uint8 with num_features), labels float32 "
+                            "[n,n_labels], sel int64 [B] with B >= 1, on one device")
+    n, s = pa.shape[0], pa.shape[1]
+    l, nl, b = text.shape[1], labels.shape[1], sel.numel()
+    f = int(num_features) if char else 0
+    out_pa = torch.empty(b, 1, s, s, dtype=torch.float32, device=pa.device)
+    out_lat = torch.empty(b, 1, s, s, dtype=torch.float32, device=pa.device)
+    out_text = torch.empty(*((b, l, f) if char else (b, l)), dtype=torch.float32, device=pa.device)
+    out_labels = torch.empty(b, nl, dtype=torch.float32, device=pa.device)
+    _check(lib().mopoe_batch_assemble(_p(pa), _p(lat), C.c_int64(n), s, _p(text), int(char), l, f, _p(labels), nl, _p(sel), b,
+                                      _p(out_pa), _p(out_lat), _p(out_text), _p(out_labels), _stream()))
+    return out_pa, out_lat, out_text, out_labels
 
 
 # ----------------------------------------------------------------------------------------------

@@ -571,12 +571,17 @@ def run_epochs(rank, exp) -> typing.List[dict]:
     exp.set_optimizer()
     from .dataio.MimicDataset import DeviceResidentMimic, Mimic
     resident = (isinstance(exp.dataset_train, Mimic) and args.device.type == "cuda"
-                and getattr(args, "device_resident_data", True) and not getattr(args, "weighted_sampler", False))
+                and getattr(args, "device_resident_data", True))
     if resident:
         # a real split lives in HBM (uint8 images + token ids): batches are gathered on the device with
-        # DistributedSampler's index rule, no worker processes and no per-step PCIe traffic (dataio.DeviceResidentMimic)
+        # DistributedSampler's index rule, no worker processes and no per-step PCIe traffic (dataio.DeviceResidentMimic).
+        # --weighted_sampler: the TRAIN rows are drawn on the device in proportion to their label weights instead
         ws, rk = (args.world_size, _rank_of(rank)) if getattr(args, "distributed", False) else (1, 0)
-        train_loader = DeviceResidentMimic(exp.dataset_train, args.device, args.batch_size, True, rk, ws, args.seed)
+        weights = exp.train_weights if getattr(args, "weighted_sampler", False) else None
+        if getattr(args, "weighted_sampler", False) and weights is None:
+            raise ValueError("weighted_sampler was set after the experiment was built: it has no train_weights")
+        train_loader = DeviceResidentMimic(exp.dataset_train, args.device, args.batch_size, True, rk, ws, args.seed,
+                                           weights=weights)
         test_loader = DeviceResidentMimic(exp.dataset_test, args.device, args.batch_size, True, rk, ws, args.seed)
     else:
         train_sampler, train_loader = get_data_loaders(args, exp.dataset_train, which_set="train",

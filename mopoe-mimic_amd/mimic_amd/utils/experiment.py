@@ -57,6 +57,9 @@ def check_flags(flags):
     if getattr(flags, "calc_nll", False) and getattr(flags, "factorized_representation", False):
         from ..evaluation.eval_metrics.likelihood import check_style_dims
         check_style_dims(flags)
+    if getattr(flags, "weighted_sampler", False) and getattr(flags, "dataset", None) == "testing":
+        raise ValueError("--weighted_sampler weights the training rows by their labels: dataset='testing' (the synthetic "
+                         "Mimic_testing) has no label table; use it with the tensor files of --dir_data")
 
 
 class HotPathExperiment:
@@ -69,6 +72,12 @@ class HotPathExperiment:
         self.labels = get_str_labels(getattr(flags, "binary_labels", False))
         # (the datasets come first, as in the reference: a real split sets flags.vocab_size / num_features for the networks)
         self.dataset_train, self.dataset_test = self.set_dataset()
+        # --weighted_sampler: the rows' sampling weights (float64 [n]), computed -- and a label table the reference's formula
+        # has no valid weights for refused -- before any network is built
+        self.train_weights = None
+        if getattr(flags, "weighted_sampler", False):
+            from ..dataio.utils import label_weights
+            self.train_weights = label_weights(self.dataset_train.labels, getattr(flags, "binary_labels", False))
         self.modalities = self.set_modalities()
         self.num_modalities = len(self.modalities)
         self.subsets = self.set_subsets()
