@@ -56,8 +56,16 @@ typedef struct {
 
 /* A BatchNorm whose normalisation is applied/inverted inside another kernel.
  * mode 0: absent.  mode 1: batch statistics from `sums` (train).  mode 2: running stats (eval).
- * mode 3 (relu_bn of mopoe_conv_dgrad* only): as mode 1, but the tensor passed as `xin` is the ACTIVATION
- *         y = relu(bn(x)) instead of x: the ReLU mask is [y > 0] and xhat = (y - beta) / gamma where it is set. */
+ * mode 3 (relu_bn of mopoe_conv_dgrad* only): the tensor passed as `xin` is the ACTIVATION y = relu(bn(x)) of a
+ *         BatchNorm of either kind (batch or running statistics) instead of x; only `gamma` and `beta` are read
+ *         (sums, rmean and rvar may be NULL).  The ReLU mask is [y > 0] and xhat = (y - beta) / gamma where it is set
+ *         (xhat = 0 where gamma == 0).
+ *         Error bound: a stored bf16 activation a2 is y rounded to nearest, |a2 - y| <= 2^-9 |y|, so
+ *         |y| <= |a2| (1 + 2^-8) and the rebuilt xhat is off by at most 2^-9 |a2| (1 + 2^-8) / |gamma| where the mask is
+ *         set; bwd_sums[1] of a channel inherits at most sum_rows |dx| * that.  It grows as |y| / |gamma|: small |gamma|
+ *         beside large |beta| is where mode 3 loses accuracy.
+ * Every entry point validates the references it is handed on the host (csrc/bn_ref_check.hpp) before anything is
+ * enqueued: a wrong mode, a missing pointer of the mode, a channel mismatch or a bad inv_count is MOPOE_ERR_ARG. */
 typedef struct {
   const double* sums;    /* [2*C] sum, sumsq over `count` rows (mode 1) */
   const float* gamma;    /* [C] */

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/mopoe_hip.h"
+#include "bn_ref_check.hpp"
 
 #define MOPOE_WAVE 64
 
@@ -12,6 +13,14 @@ namespace mopoe {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+
+// check_bn_ref (bn_ref_check.hpp) with its message handed to mopoe_last_error()
+inline int bn_ref_ok(const mopoe_bn_ref* b, int C, bool allow_mode3, const char* who) {
+  char msg[256];
+  const int rc = check_bn_ref(b, C, allow_mode3, who, msg, sizeof msg);
+  if (rc) set_error("%s", msg);
+  return rc;
+}
 
 // ---- BatchNorm coefficients from a mopoe_bn_ref --------------------------------------------------
 struct BnC {
@@ -24,7 +33,20 @@ __device__ __forceinline__ BnC bn_coef(const mopoe_bn_ref& b, int c) {
   r.mean = 0.f; r.rstd = 1.f; r.scale = 1.f; r.shift = 0.f;
   return r;
 #endif
-  if (b.mode == 1 || b.mode == 3) {
+  if (b.mode == 3) {
+    // the tensor that will be read is the ACTIVATION y = relu(gamma * xhat + beta) of this BatchNorm (of either kind,
+    // batch or running statistics), not its input (conv2's input gradient when the block front is recomputed,
+    // pointwise.hip): [y > 0] is the ReLU mask and xhat = (y - beta) / gamma wherever the mask is set -- the only places
+    // the masked gradient looks at xhat.  Only gamma and beta are read: sums, rmean and rvar may be NULL
+    // (mopoe_hip.h states the error bound of the rebuilt xhat)
+    const float g = b.gamma[c];
+    r.mean = b.beta[c];
+    r.rstd = g != 0.f ? 1.0f / g : 0.f;
+    r.scale = 1.f;
+    r.shift = 0.f;
+    return r;
+  }
+  if (b.mode == 1) {
     const double m = b.sums[c] * b.inv_count;
     double v = b.sums[b.C + c] * b.inv_count - m * m;
     v = v < 0.0 ? 0.0 : v;
@@ -37,17 +59,6 @@ __device__ __forceinline__ BnC bn_coef(const mopoe_bn_ref& b, int c) {
   const float g = b.gamma[c];
   r.scale = g * r.rstd;
   r.shift = b.beta[c] - r.mean * r.scale;
-  if (b.mode == 3) {
-    // the tensor that will be read is the ACTIVATION y = relu(scale * x + shift) of this (batch-statistics) BatchNorm, not x
-    // (conv2's input gradient when the block front is recomputed, pointwise.hip): [y > 0] is the ReLU mask and
-    // xhat = (y - beta) / gamma wherever the mask is set -- the only places the masked gradient looks at xhat
-    BnC y;
-    y.mean = b.beta[c];
-    y.rstd = g != 0.f ? 1.0f / g : 0.f;
-    y.scale = 1.f;
-    y.shift = 0.f;
-    return y;
-  }
   return r;
 }
 

@@ -1150,6 +1150,7 @@ extern "C" int mopoe_conv_fwd(const float* x, const float* wp, const float* bias
                               const mopoe_conv_plan* plan, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !wp || !y) { set_error("conv_fwd: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(bn_in, g->Cin, false, "mopoe_conv_fwd: bn_in")) return rc;
   const bool plain = (!bn_in || bn_in->mode == 0) && (!mask || mask->kind == 0);
   // image-side edge layers: one channel on one side -> streaming kernels instead of a 98 %-padding GEMM tile
   if (plain && !g->transposed && g->Cin == 1 && !bias && edge_supported(g, g->Cout, {wp, y}))
@@ -1167,6 +1168,8 @@ extern "C" int mopoe_conv_fwd_mix(const float* x, const float* wp, const float* 
                                   void* stream) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !wp || !y || !mix) { set_error("conv_fwd_mix: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(bn_in, g->Cin, false, "mopoe_conv_fwd_mix: bn_in")) return rc;
+  if (int rc = bn_ref_ok(&mix->bn, g->Cout, false, "mopoe_conv_fwd_mix: mix->bn")) return rc;
   return launch_gather(x, wp, bias, y, g, g->transposed ? 0 : 1, g->Cin, g->Cout, /*w_nk=*/0, bn_in, mask, out_stats,
                        nullptr, nullptr, nullptr, plan, workspace, workspace_bytes, (hipStream_t)stream, mix);
 }
@@ -1176,6 +1179,8 @@ extern "C" int mopoe_conv_dgrad(const float* dy, const float* wp, float* dx, con
                                 const mopoe_conv_plan* plan, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = validate_geom(g)) return rc;
   if (!dy || !wp || !dx) { set_error("conv_dgrad: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(relu_bn, g->Cin, true, "mopoe_conv_dgrad: relu_bn")) return rc;
+  if (relu_bn && relu_bn->mode != 0 && !xin) { set_error("mopoe_conv_dgrad: relu_bn needs xin"); return MOPOE_ERR_ARG; }
   if (g->transposed && g->Cout == 1 && (!relu_bn || relu_bn->mode == 0) && edge_supported(g, g->Cin, {wp, dx}))
     return edge_expand(dy, wp, dx, g, g->Cin, nullptr, (hipStream_t)stream);
   // input gradient of a Conv lives on the big grid (phases); of a ConvTranspose on the small grid.
@@ -1214,6 +1219,7 @@ extern "C" int mopoe_conv_wgrad(const float* x, const float* dy, float* dwp, con
                                 void* stream_) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !dy || !dwp) { set_error("conv_wgrad: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(bn_in, g->Cin, false, "mopoe_conv_wgrad: bn_in")) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   if ((!bn_in || bn_in->mode == 0) && !g->transposed && g->Cin == 1 && edge_supported(g, g->Cout, {dy, dwp}))
     return edge_wgrad(dy, x, dwp, g, g->Cout, stream, dwp_is_zero != 0);

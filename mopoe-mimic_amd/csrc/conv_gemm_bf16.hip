@@ -615,6 +615,7 @@ extern "C" int mopoe_conv_fwd_bf16(const uint16_t* x, const uint16_t* wp, const 
                                    void* stream) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !wp || !y) { set_error("conv_fwd_bf16: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(bn_in, g->Cin, false, "mopoe_conv_fwd_bf16: bn_in")) return rc;
   return launch_gather_bf16(x, wp, bias, y, y_is_f32, g, g->transposed ? 0 : 1, g->Cin, g->Cout, /*w_nk=*/0, bn_in, mask,
                             out_stats, nullptr, nullptr, nullptr, plan, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -625,6 +626,8 @@ extern "C" int mopoe_conv_fwd_mix_bf16(const uint16_t* x, const uint16_t* wp, co
                                        void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !wp || !y || !mix) { set_error("conv_fwd_mix_bf16: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(bn_in, g->Cin, false, "mopoe_conv_fwd_mix_bf16: bn_in")) return rc;
+  if (int rc = bn_ref_ok(&mix->bn, g->Cout, false, "mopoe_conv_fwd_mix_bf16: mix->bn")) return rc;
   return launch_gather_bf16(x, wp, bias, y, 0, g, g->transposed ? 0 : 1, g->Cin, g->Cout, /*w_nk=*/0, bn_in, mask,
                             out_stats, nullptr, nullptr, nullptr, plan, workspace, workspace_bytes, (hipStream_t)stream, mix);
 }
@@ -635,6 +638,8 @@ extern "C" int mopoe_conv_dgrad_bf16(const uint16_t* dy, const uint16_t* wp, voi
                                      void* stream) {
   if (int rc = validate_geom(g)) return rc;
   if (!dy || !wp || !dx) { set_error("conv_dgrad_bf16: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(relu_bn, g->Cin, true, "mopoe_conv_dgrad_bf16: relu_bn")) return rc;
+  if (relu_bn && relu_bn->mode != 0 && !xin) { set_error("mopoe_conv_dgrad_bf16: relu_bn needs xin"); return MOPOE_ERR_ARG; }
   return launch_gather_bf16(dy, wp, nullptr, dx, dx_is_f32, g, g->transposed ? 1 : 0, g->Cout, g->Cin, /*w_nk=*/1, nullptr,
                             nullptr, nullptr, relu_bn, xin, bwd_sums, plan, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -675,6 +680,7 @@ extern "C" int mopoe_conv_wgrad_bf16(const uint16_t* x, const uint16_t* dy, floa
                                      void* stream_) {
   if (int rc = validate_geom(g)) return rc;
   if (!x || !dy || !dwp) { set_error("conv_wgrad_bf16: null pointer"); return MOPOE_ERR_ARG; }
+  if (int rc = bn_ref_ok(bn_in, g->Cin, false, "mopoe_conv_wgrad_bf16: bn_in")) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   const mopoe_bn_ref none = {};
   WgradArgsH a;

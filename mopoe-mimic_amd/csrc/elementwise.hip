@@ -444,9 +444,18 @@ static bool ew_wide_ok(int C, std::initializer_list<const void*> ptrs, const cha
   return ok;
 }
 
+// "mopoe_<entry point>[_bf16]: <argument>" for bn_ref_ok (one static buffer per thread: the name is read before the next call)
+template <typename T>
+static const char* ew_who(const char* entry, const char* arg) {
+  static thread_local char who[96];
+  snprintf(who, sizeof who, "mopoe_%s%s: %s", entry, std::is_same<T, bf16_t>::value ? "_bf16" : "", arg);
+  return who;
+}
+
 template <typename T>
 static int bn_relu_apply_t(const T* x, T* out, int64_t rows, int32_t C, const mopoe_bn_ref* bn, void* stream) {
   EW_ARGCHECK(x && out && bn && bn->mode != 0 && bn->C == C && rows > 0, "bn_relu_apply: bad arguments");
+  if (int rc = bn_ref_ok(bn, C, false, ew_who<T>("bn_relu_apply", "bn"))) return rc;
   hipStream_t st = (hipStream_t)stream;
   int rc;
   constexpr int W = EwVec<T>::wide;
@@ -463,6 +472,7 @@ template <typename T>
 static int block_out_fwd_t(const T* s, const T* m, T* out, int64_t rows, int32_t C, const mopoe_bn_ref* bn_s, float a,
                            float b, double* out_stats, void* stream) {
   EW_ARGCHECK(s && m && out && bn_s && bn_s->mode != 0 && bn_s->C == C && rows > 0, "block_out_fwd: bad arguments");
+  if (int rc = bn_ref_ok(bn_s, C, false, ew_who<T>("block_out_fwd", "bn_s"))) return rc;
   hipStream_t st = (hipStream_t)stream;
   int rc;
   constexpr int W = EwVec<T>::wide;
@@ -479,6 +489,7 @@ template <typename T>
 static int bn_bwd_reduce_t(const T* g, const T* s, int64_t rows, int32_t C, const mopoe_bn_ref* bn_s, double* sums,
                            void* stream) {
   EW_ARGCHECK(g && s && sums && bn_s && bn_s->mode != 0 && bn_s->C == C && rows > 0, "bn_bwd_reduce: bad arguments");
+  if (int rc = bn_ref_ok(bn_s, C, false, ew_who<T>("bn_bwd_reduce", "bn_s"))) return rc;
   hipStream_t st = (hipStream_t)stream;
   int rc;
   constexpr int W = EwVec<T>::wide;
@@ -497,6 +508,7 @@ static int block_out_bwd_t(const T* g, const T* s, T* dm, T* ds, int64_t rows, i
                            float* colsum_dm, float* colsum_ds, void* stream) {
   EW_ARGCHECK(g && s && dm && ds && sums && dgamma && dbeta && bn_s && bn_s->mode != 0 && bn_s->C == C && rows > 0,
               "block_out_bwd: bad arguments");
+  if (int rc = bn_ref_ok(bn_s, C, false, ew_who<T>("block_out_bwd", "bn_s"))) return rc;
   mopoe_mask_ref mk = mask ? *mask : mopoe_mask_ref{nullptr, 0, 1};
   hipStream_t st = (hipStream_t)stream;
   int rc;
@@ -519,6 +531,8 @@ static int bn_bwd_apply_t(const T* dy, const T* x, const T* add, T* dx, int64_t 
   const bool next = next_s != nullptr;
   EW_ARGCHECK(!next || (next_bn && next_sums && next_bn->mode != 0 && next_bn->C == C),
               "bn_bwd_apply: next_s needs next_bn (C channels) and next_sums");
+  if (int rc = bn_ref_ok(bn, C, false, ew_who<T>("bn_bwd_apply", "bn"))) return rc;
+  if (next) if (int rc = bn_ref_ok(next_bn, C, false, ew_who<T>("bn_bwd_apply", "next_bn"))) return rc;
   mopoe_mask_ref mk = mask ? *mask : mopoe_mask_ref{nullptr, 0, 1};
   const mopoe_bn_ref nb = next ? *next_bn : mopoe_bn_ref{};
   hipStream_t st = (hipStream_t)stream;

@@ -875,6 +875,11 @@ static int pw_check(const char* what, const void* x, const void* W, int64_t rows
   if (!x || !W || rows <= 0 || !bn1 || bn1->mode == 0 || bn1->C != C) { set_error("%s: bad arguments", what); return MOPOE_ERR_ARG; }
   if (C != 64) { set_error("%s: built for 64 channels (C = %d)", what, C); return MOPOE_ERR_ARG; }
   if (bn2 && (bn2->mode == 0 || bn2->C != C)) { set_error("%s: bn2 channel mismatch", what); return MOPOE_ERR_ARG; }
+  char who[96];
+  snprintf(who, sizeof who, "mopoe_%s: bn1", what);
+  if (int rc = bn_ref_ok(bn1, C, false, who)) return rc;
+  snprintf(who, sizeof who, "mopoe_%s: bn2", what);
+  if (int rc = bn_ref_ok(bn2, C, false, who)) return rc;
   if (mask && mask->kind != 0 && (mask->kind != 1 || !mask->mask || mask->rows_per_sample % 32 != 0)) {
     set_error("%s: dropout mask must be absent or per (sample, channel) with rows_per_sample a multiple of 32", what); return MOPOE_ERR_ARG;
   }

@@ -124,7 +124,7 @@ class Bn:
     """A BatchNorm to be applied / inverted inside another kernel (header: mopoe_bn_ref)."""
     gamma: torch.Tensor
     beta: torch.Tensor
-    mode: int                               # 1 batch statistics, 2 running statistics, 3 = 1 with the ACTIVATION as xin (conv_dgrad)
+    mode: int                               # 1 batch statistics, 2 running statistics, 3 = the ACTIVATION is xin (conv_dgrad): gamma, beta only
     sums: Optional[torch.Tensor] = None     # double [2, C] (mode 1)
     count: int = 0                          # rows the sums were taken over (mode 1)
     rmean: Optional[torch.Tensor] = None

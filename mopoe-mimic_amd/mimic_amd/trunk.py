@@ -314,8 +314,9 @@ def trunk_backward(blocks: List[BlockSpec], saved, g, grads: Dict[str, torch.Ten
         a2 = sv.get("a2")
         front = bool(sv.get("front_bwd"))      # the fused backward of the block's front (csrc/pointwise.hip)
         if d1 is None:      # (the forward ran the streaming front too: d1 was never written)
-            # conv2's input gradient reads its ReLU mask and x-hat off a2 = relu(bn2(d1)) (mopoe_bn_ref mode 3)
-            bn2y = Bn(bn2.gamma, bn2.beta, 3, sums=bn2.sums, count=bn2.count, eps=bn2.eps)
+            # conv2's input gradient reads its ReLU mask and x-hat off a2 = relu(bn2(d1)) (mopoe_bn_ref mode 3: gamma and beta
+            # alone, whichever statistics bn2 normalised with -- after an eval-mode forward it has no sums)
+            bn2y = Bn(bn2.gamma, bn2.beta, 3, eps=bn2.eps)
             dh2 = ops.conv_dgrad(dm, wsel(p.conv2), g2, relu_bn=bn2y, xin=a2, bwd_sums=sums2)
         else:
             dh2 = ops.conv_dgrad(dm, wsel(p.conv2), g2, relu_bn=bn2, xin=d1, bwd_sums=sums2)

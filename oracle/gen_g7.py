@@ -40,6 +40,9 @@ from golden_util import pack_grad, pack_bits, weights_fingerprint, rec_sample_in
 C2 = dict(img_size=128, class_dim=128, DIM_img=64, DIM_text=128, vocab_size=3517)
 C5 = dict(img_size=256, class_dim=256, DIM_img=64, DIM_text=128, vocab_size=3517)
 SMALL = dict(img_size=64, class_dim=32, DIM_img=32, DIM_text=32, vocab_size=200)
+# the smallest configuration with 64-channel 1x1 residual blocks in both the image and the text networks: the streaming block
+# front (csrc/pointwise.hip) and the mode-3 input gradient of conv2 exist only there
+EVAL64 = dict(img_size=64, class_dim=32, DIM_img=64, DIM_text=64, vocab_size=200)
 # name -> (cfg kwargs, rows, seed, mode, family, truth); seeds / modes are the ones the round-3 live-oracle tests used
 CASES = {
     "c2_b8": (C2, 8, 21, "train_nodrop", "fp32", "ref64"),
@@ -52,11 +55,21 @@ CASES = {
     "c3_b256_bf16": (C2, 256, 91, "train_nodrop", "bf16", "ref32"),
     "c5_b32_bf16": (C5, 32, 95, "train_nodrop", "bf16", "ref32"),
     # a small configuration the bf16 family accepts (every GEMM K a multiple of 32): BatchNorm batch statistics, dropout (the
-    # oracle's seeded masks: its fp32 pass is then the oracle's too), eval (running statistics, forward only)
+    # oracle's seeded masks: its fp32 pass is then the oracle's too), eval (running statistics; the oracle's fp32 pass, whose
+    # forward entries the first version of this fixture already held)
     "small_bf16_nodrop": (SMALL, 8, 71, "train_nodrop", "bf16", "ref32"),
     "small_bf16_dropout": (SMALL, 8, 72, "train", "bf16", "oracle32"),
     "small_bf16_eval": (SMALL, 8, 73, "eval", "bf16", "oracle32"),
+    # a backward pass taken in eval mode (running statistics in every BatchNorm) at 64 channels, both storage families
+    "eval64_b8": (EVAL64, 8, 75, "eval", "fp32", "ref64"),
+    "eval64_b8_bf16": (EVAL64, 8, 77, "eval", "bf16", "ref32"),
 }
+# cases whose committed fixture a regeneration must reproduce entry for entry (it may only add arrays)
+KEEP_ENTRIES = ("small_bf16_eval",)
+# cases whose fp32 gradients (g32/*) go into a companion file g7_<case>_g32.npz, which keeps each file below 1 MiB
+SPLIT_G32 = ("small_bf16_eval", "eval64_b8_bf16")
+
+
 def scalars_to_store(store, prefix, total, klds, log_probs):
     store[f"{prefix}/total_loss"] = np.array(float(total))
     for k, v in klds.items():
@@ -72,12 +85,12 @@ def rec_to_store(store, prefix, rec):
         store[f"{prefix}/recmax/{m}"] = np.array(t.abs().max().item())
 
 
-def reference_pass(run_epochs, cfg, sd, batch, eps, dtype):
-    """the reference's fwd + bwd in `dtype` on the given inputs / noise: (out, {name: grad})"""
+def reference_pass(run_epochs, cfg, sd, batch, eps, dtype, mode="train_nodrop"):
+    """the reference's fwd + bwd in `dtype` on the given inputs / noise, in train_nodrop or eval mode: (out, {name: grad})"""
     exp = GG.build_reference(cfg, sd)
     exp.mm_vae.to(dtype)
     b = {k: v.to(dtype) for k, v in batch.items()}
-    out, _ = GG.run_reference(run_epochs, exp, b, "train_nodrop", force_eps=eps.to(dtype))
+    out, _ = GG.run_reference(run_epochs, exp, b, mode, force_eps=eps.to(dtype))
     grads = {n: p.grad.detach().clone() for n, p in exp.mm_vae.named_parameters() if p.grad is not None}
     return out, grads
 
@@ -90,8 +103,8 @@ def oracle_pass(cfg, sd, batch, eps, mk_ctx, dtype=torch.float32):
     return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}, grads
 
 
-def break_ties_reference(run_epochs, cfg, sd, batch, eps, margin=2e-3):
-    """gen_golden.break_ties' rule with the reference's forward on the given noise (train_nodrop)"""
+def break_ties_reference(run_epochs, cfg, sd, batch, eps, margin=2e-3, mode="train_nodrop"):
+    """gen_golden.break_ties' rule with the reference's forward on the given noise (train_nodrop or eval)"""
     direction = {m: torch.where(batch[m] < 0.5, 2.0, -2.0) for m in ("PA", "Lateral")}
     exp = GG.build_reference(cfg, sd)
     model = exp.mm_vae
@@ -99,6 +112,8 @@ def break_ties_reference(run_epochs, cfg, sd, batch, eps, margin=2e-3):
     for mod in model.modules():
         if isinstance(mod, (torch.nn.Dropout, torch.nn.Dropout2d)):
             mod.eval()
+    if mode == "eval":
+        model.eval()
     running = {k: v.clone() for k, v in model.state_dict().items()}
     for it in range(40):
         model.load_state_dict(running)          # (train-mode forwards move the BatchNorm running statistics)
@@ -184,27 +199,20 @@ def gen_case(run_epochs, name):
         if mode == "train":
             batch = break_ties_oracle(cfg, sd, batch, eps, mk)
         else:
-            batch = break_ties_reference(run_epochs, cfg, sd, batch, eps)
+            batch = break_ties_reference(run_epochs, cfg, sd, batch, eps, mode=mode)
     moved_pixels(store, batch0, batch)
     store["in/fingerprint"] = np.array([batch["PA"].double().sum().item(), batch["Lateral"].double().sum().item(),
                                         batch["text"].double().sum().item(), eps.double().sum().item()])
     print(f"[{name}] inputs ready ({time.time() - t0:.0f} s)")
 
     # ---- the fp32 pass of the reference arithmetic (the reference itself unless dropout masks must be replayed)
-    if mode == "eval":          # forward only (running statistics): scalars and reconstructions of both arithmetics
-        with torch.no_grad():
-            o32 = R.forward_step(cfg, sd, batch, eps, mk())
-            o16 = R.forward_step(cfg, sd, batch, eps, mk(bf16=True))
-        for tag, o in (("fp32", o32), ("bf16", o16)):
-            scalars_to_store(store, tag, o["total_loss"], o["klds"], o["log_probs"])
-            rec_to_store(store, tag, o["rec"])
-        return store
+    # (an eval case stores gradients exactly as a train_nodrop case does: a backward pass in eval mode is supported)
     o32, go32 = oracle_pass(cfg, sd, batch, eps, mk)
-    if mode == "train":
+    if truth.startswith("oracle"):
         out32 = dict(total_loss=o32["total_loss"], klds=o32["klds"], log_probs=o32["log_probs"], rec=o32["rec"])
         g32 = go32
     else:
-        out, g32 = reference_pass(run_epochs, cfg, sd, batch, eps, torch.float32)
+        out, g32 = reference_pass(run_epochs, cfg, sd, batch, eps, torch.float32, mode)
         out32 = dict(total_loss=out["total_loss"].detach(), klds={k: v.detach() for k, v in out["klds"].items()},
                      log_probs={k: v.detach() for k, v in out["log_probs"].items()},
                      rec={m: out["results"]["rec"][m].loc.detach() for m in ("PA", "Lateral")})
@@ -223,7 +231,7 @@ def gen_case(run_epochs, name):
     store["grad_numel"] = np.array([g32[n].numel() for n in names])
     if family == "fp32":
         if truth == "ref64":
-            _, g64 = reference_pass(run_epochs, cfg, sd, batch, eps, torch.float64)
+            _, g64 = reference_pass(run_epochs, cfg, sd, batch, eps, torch.float64, mode)
         elif truth == "oracle64":
             _, g64 = oracle_pass(cfg, sd, batch, eps, mk, torch.float64)
         else:
@@ -317,6 +325,16 @@ def main():
             continue
         store = job()
         path = os.path.join(outdir, f"g7_{name}.npz")
+        if name in KEEP_ENTRIES and os.path.exists(path):
+            with np.load(path) as old:
+                for k in old.files:
+                    assert k in store and np.array_equal(old[k], np.asarray(store[k])), f"{name}: entry {k} of the committed fixture changed"
+                print(f"[{name}] all {len(old.files)} entries of the committed fixture reproduced exactly")
+        if name in SPLIT_G32:
+            side = {k: store.pop(k) for k in [k for k in store if k.startswith("g32/")]}
+            side_path = os.path.join(outdir, f"g7_{name}_g32.npz")
+            np.savez_compressed(side_path, **side)
+            print(f"wrote {side_path}: {os.path.getsize(side_path) / 1024:.0f} KiB, {len(side)} arrays")
         np.savez_compressed(path, **store)
         print(f"wrote {path}: {os.path.getsize(path) / 1024:.0f} KiB, {len(store)} arrays")
 

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 import mopoe_ref as R
-from golden_util import (load, cfg_from, PackedGrad, unpack_mask, weights_fingerprint, rec_sample_index)
+from golden_util import (GOLDEN, load, cfg_from, PackedGrad, unpack_mask, weights_fingerprint, rec_sample_index)
 from model_util import build_exp
 from mimic_amd import run_epochs as RE
 
@@ -156,12 +156,13 @@ def check_bf16_case(case, small_batch=False, grads=True):
     grads = exp.mm_vae.reference_named_grads()
     names, numel, meta = [str(n) for n in g["grad_names"]], g["grad_numel"], g["grad_meta"]
     assert set(grads) == set(names)
+    g32 = load(f"g7_{case}_g32") if os.path.exists(os.path.join(GOLDEN, f"g7_{case}_g32.npz")) else g    # (oracle/gen_g7.py: SPLIT_G32)
     cap, cos_min, med_max, p90_max = (0.22, 0.975, 6e-2, 0.15) if small_batch else (0.15, 0.985, 4e-2, 0.11)
     bad, cos_all, rel_reg = [], [], []
     for name, n, (scale, e_ref32) in zip(names, numel, meta):
         gr = grads[name]
         assert torch.isfinite(gr).all(), name
-        b, c = PackedGrad(g, f"g16/{name}", int(n)), PackedGrad(g, f"g32/{name}", int(n))
+        b, c = PackedGrad(g, f"g16/{name}", int(n)), PackedGrad(g32, f"g32/{name}", int(n))
         floor = 2e-2 * scale * int(n) ** 0.5          # bf16 noise floor for (near-)zero gradients
         below = b.norm <= floor
         d16, _, na = b.diff(gr)

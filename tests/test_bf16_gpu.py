@@ -124,11 +124,12 @@ def _conv_case(name, g: Geom, plan=None):
         check(f"{name}/dgrad_relubn{mode}/sums", s, s_ref, rtol=2e-3, atol_rel=2e-3)
     # weight gradient (fp32 result)
     check(f"{name}/wgrad", ops.conv_wgrad(xd, dyd, g), TB.conv_wgrad(x, dy, g), rtol=3e-4, atol_rel=3e-4)
-    bn = make_bn(g.Cin, rows_in, 1, gen, x.float())
-    # (the BN+ReLU'd operand is rounded to bf16 on both sides, from an fma here and a multiply-add there: a few
-    # operand elements round the other way, which moves a weight gradient more than fp32 summation order does)
-    check(f"{name}/wgrad_bn", ops.conv_wgrad(xd, dyd, g, bn_in=to_dev(bn)), TB.conv_wgrad(x, dy, g, bn_in=bn),
-          rtol=2e-3, atol_rel=1e-3)
+    for mode in (1, 2):
+        bn = make_bn(g.Cin, rows_in, mode, gen, x.float() if mode == 1 else None)
+        # (the BN+ReLU'd operand is rounded to bf16 on both sides, from an fma here and a multiply-add there: a few
+        # operand elements round the other way, which moves a weight gradient more than fp32 summation order does)
+        check(f"{name}/wgrad_bn" + ("" if mode == 1 else "2"), ops.conv_wgrad(xd, dyd, g, bn_in=to_dev(bn)),
+              TB.conv_wgrad(x, dy, g, bn_in=bn), rtol=2e-3, atol_rel=1e-3)
 
 
 @pytest.mark.parametrize("name,g", GEOMS16, ids=[n for n, _ in GEOMS16])
@@ -350,11 +351,17 @@ def test_edge_layers_bf16(n, hs, ws):
 
 @pytest.mark.parametrize("rows,c", [(4096, 64), (300, 320), (7, 640), (70000, 128)])
 def test_block_glue_bf16(rows, c):
-    gen = torch.Generator().manual_seed(rows + c)
+    # (running statistics, mode 2: a backward pass taken in eval mode -- at the two shapes with ragged row counts)
+    for mode in ((1, 2) if (rows, c) in ((300, 320), (7, 640)) else (1,)):
+        _block_glue_bf16(rows, c, mode)
+
+
+def _block_glue_bf16(rows, c, mode):
+    gen = torch.Generator().manual_seed(rows + c + 7919 * (mode - 1))
     s = torch.randn(rows, c, generator=gen).to(BF)
     m = torch.randn(rows, c, generator=gen).to(BF)
     g = torch.randn(rows, c, generator=gen).to(BF)
-    bn = make_bn(c, rows, 1, gen, s.float())
+    bn = make_bn(c, rows, mode, gen, s.float() if mode == 1 else None)
     sd, md, gd, bnd = s.to(DEV), m.to(DEV), g.to(DEV), to_dev(bn)
     st_ref, st = torch.zeros(2, c, dtype=torch.float64), torch.zeros(2, c, dtype=torch.float64, device=DEV)
     check16("bn_relu_apply", ops.bn_relu_apply(sd, bnd), TB.bn_relu_apply(s, bn))
@@ -368,6 +375,10 @@ def test_block_glue_bf16(rows, c):
     ref = TB.block_out_bwd(g, s, bn, sums_ref, mask, want_colsum_dm=True)
     got = ops.block_out_bwd(gd, sd, bnd, sums_ref.to(DEV), to_dev(mask), want_colsum_dm=True)
     for nm, a, b in zip(("dm", "ds", "dgamma", "dbeta", "cdm", "cds"), got, ref):
+        if nm == "cds" and mode == 2:
+            # running statistics: ds = a gamma rstd g has no batch terms, its column sums are ordinary sums (the bar of cdm)
+            check("block_out_bwd/cds_bn2", a, b, rtol=2e-3, atol_rel=2e-3)
+            continue
         if nm == "cds":
             # the column sums of a BatchNorm backward are analytically zero: what is left is the rounding of the stored
             # elements, so the bound is one rounding step of an element times sqrt(rows), not a fraction of the sum
@@ -377,7 +388,7 @@ def test_block_glue_bf16(rows, c):
         (check16 if a.dtype == BF else (lambda k, u, v: check(k, u, v, rtol=2e-3, atol_rel=2e-3)))(f"block_out_bwd/{nm}", a, b)
     x = torch.randn(rows, c, generator=gen).to(BF)
     add = torch.randn(rows, c, generator=gen).to(BF)
-    bnx = make_bn(c, rows, 1, gen, x.float())
+    bnx = make_bn(c, rows, mode, gen, x.float() if mode == 1 else None)
     dy = g
     sums_x = torch.stack([dy.float().double().sum(0), (dy.float() * ((x.float() - TB.bn_coef(bnx)[0]) * TB.bn_coef(bnx)[1])).double().sum(0)])
     nsum_ref, nsum = torch.zeros(2, c, dtype=torch.float64), torch.zeros(2, c, dtype=torch.float64, device=DEV)
@@ -392,16 +403,22 @@ def test_block_glue_bf16(rows, c):
 
 @pytest.mark.parametrize("n,rps,drop", [(3, 64, True), (2, 1024, False), (5, 32, True), (1, 4096, True)])
 def test_block_front_streaming_kernels_bf16(n, rps, drop):
+    front_case_bf16(n, rps, drop, 1, 1)
+
+
+def front_case_bf16(n, rps, drop, mode1, mode2):
     """csrc/pointwise.hip (round 4): the front of a residual block -- bn1 -> relu -> conv1 (1x1, 64 channels) -> Dropout2d -> bn2
     -> relu -- without ever writing d1: statistics pass, a2 pass and the fused backward (bn2 backward + conv1 input / weight
     gradients + bn1's backward sums) against the emulation, which composes exactly the ops these kernels replace; then the
-    replaced HIP ops themselves (conv_fwd + bn_relu_apply / bn_bwd_apply + conv_dgrad + conv_wgrad) on the same inputs."""
+    replaced HIP ops themselves (conv_fwd + bn_relu_apply / bn_bwd_apply + conv_dgrad + conv_wgrad) on the same inputs.
+    mode1 / mode2: batch (1) or running (2) statistics in bn1 / bn2 -- (2, 2) is a backward pass taken in eval mode
+    (tests/test_bn_modes_gpu.py runs the modes beside (1, 1))."""
     c, rows = 64, n * rps
-    gen = torch.Generator().manual_seed(n * 1000 + rps)
+    gen = torch.Generator().manual_seed(n * 1000 + rps + 10 * mode1 + 100 * mode2 - 110)
     x = torch.randn(rows, c, generator=gen).to(BF).view(n, rps, 1, c)
     w1 = (torch.randn(1, c, c, generator=gen) / 8).to(BF)
     bias = 0.1 * torch.randn(c, generator=gen)
-    bn1 = make_bn(c, rows, 1, gen, x.float())
+    bn1 = make_bn(c, rows, mode1, gen, x.float() if mode1 == 1 else None)
     mask = Mask((torch.rand(n, c, generator=gen) < 0.5).float() * 2, 1, rps) if drop else None
     g1 = Geom(n, rps, 1, rps, 1, c, c, 1, 1, 1, 1, 0, 0, False)
     assert ops.block_front_supported(x.to(DEV), g1, to_dev(mask))
@@ -416,6 +433,11 @@ def test_block_front_streaming_kernels_bf16(n, rps, drop):
     d1_old = ops.conv_fwd(xd, wd, g1, bn_in=bn1d, bias=bd, mask=md, out_stats=st_old)
     check("front/stats_vs_conv_fwd", st, st_old, rtol=2e-3, atol_rel=2e-3)
     bn2 = Bn(torch.rand(c, generator=gen) + 0.5, 0.1 * torch.randn(c, generator=gen), 1, st_ref.clone(), rows)
+    if mode2 == 2:      # running statistics near d1's own, as a trained model's are
+        mean_d1 = (st_ref[0] / rows).float()
+        var_d1 = (st_ref[1] / rows).float() - mean_d1 * mean_d1
+        bn2 = Bn(bn2.gamma, bn2.beta, 2, rmean=mean_d1 + 0.1 * torch.randn(c, generator=gen),
+                 rvar=var_d1 * (0.75 + 0.5 * torch.rand(c, generator=gen)))
     bn2d = to_dev(bn2)
     a2_ref = TB.block_front_apply(x, w1, bias, bn1, bn2, mask)
     a2 = ops.block_front_apply(xd, wd, bd, bn1d, bn2d, md)
@@ -452,7 +474,8 @@ def test_block_front_streaming_kernels_bf16(n, rps, drop):
     check("front/sums1_vs_old_ops", s1, s1_old, rtol=5e-3, atol_rel=5e-3)
     check("front/dw1_vs_old_ops", dw, ops.conv_wgrad(xd, dc1_old, g1, bn_in=bn1d), rtol=2e-3, atol_rel=2e-3)
     assert (db - cdc1_old).abs().max().item() <= noise, ((db - cdc1_old).abs().max().item(), noise)
-    # conv2's input gradient with its ReLU mask / x-hat taken from a2 (bn mode 3) == from d1 (mode 1)
+    # conv2's input gradient with its ReLU mask / x-hat taken from a2 (bn mode 3: gamma and beta alone, no sums) == from d1
+    # (bn2 itself, mode 1 or 2)
     g2 = Geom(n, 1, rps // 2, 1, rps, c, 128, 1, 4, 1, 2, 0, 1, False) if rps % 2 == 0 else None
     if g2 is not None:
         w2 = (torch.randn(g2.taps, c, 128, generator=gen) / 16).to(BF).to(DEV)
@@ -460,7 +483,7 @@ def test_block_front_streaming_kernels_bf16(n, rps, drop):
         xa = d1_old.view(g2.in_shape)
         sa, sb = torch.zeros(2, c, dtype=torch.float64, device=DEV), torch.zeros(2, c, dtype=torch.float64, device=DEV)
         ga = ops.conv_dgrad(dm, w2, g2, relu_bn=bn2d, xin=xa, bwd_sums=sa)
-        bn2y = Bn(bn2d.gamma, bn2d.beta, 3, sums=bn2d.sums, count=bn2d.count)
+        bn2y = Bn(bn2d.gamma, bn2d.beta, 3)
         gb = ops.conv_dgrad(dm, w2, g2, relu_bn=bn2y, xin=a2.view(g2.in_shape), bwd_sums=sb)
         check16("front/conv2_dgrad_mask_from_a2", gb, ga.cpu())
         check("front/conv2_dgrad_sums_from_a2", sb, sa, rtol=2e-2, atol_rel=2e-2)    # (x-hat through the bf16-rounded a2)
@@ -499,7 +522,7 @@ def test_small_model_bf16_vs_oracle():
     B = 8): BatchNorm batch statistics, dropout (the oracle's seeded masks replayed), eval -- fixtures G7 small_bf16_*"""
     check_bf16_case("small_bf16_nodrop", small_batch=True)
     check_bf16_case("small_bf16_dropout", small_batch=True)
-    check_bf16_case("small_bf16_eval", grads=False)
+    check_bf16_case("small_bf16_eval", small_batch=True)      # (a backward pass in eval mode: running statistics)
 
 
 def test_c3_full_size_bf16(table_plans):

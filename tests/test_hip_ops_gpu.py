@@ -135,10 +135,11 @@ def test_conv_family(name, g: Geom):
     dw_ref = TB.conv_wgrad(x, dy, g)
     dw = ops.conv_wgrad(x.to(DEV), dy.to(DEV), g)
     check(f"{name}/wgrad", dw, dw_ref)
-    bn = make_bn(g.Cin, rows_in, 1, gen, x)
-    dw_ref = TB.conv_wgrad(x, dy, g, bn_in=bn)
-    dw = ops.conv_wgrad(x.to(DEV), dy.to(DEV), g, bn_in=to_dev(bn))
-    check(f"{name}/wgrad_bn", dw, dw_ref)
+    for mode in (1, 2):
+        bn = make_bn(g.Cin, rows_in, mode, gen, x if mode == 1 else None)
+        dw_ref = TB.conv_wgrad(x, dy, g, bn_in=bn)
+        dw = ops.conv_wgrad(x.to(DEV), dy.to(DEV), g, bn_in=to_dev(bn))
+        check(f"{name}/wgrad_bn" + ("" if mode == 1 else "2"), dw, dw_ref)
 
 
 @pytest.mark.parametrize("name,g", [
@@ -655,15 +656,21 @@ def test_token_softmax_grad(b, L, V, out_dtype):
 
 @pytest.mark.parametrize("n,rps,drop", [(3, 64, True), (2, 1024, False), (5, 32, True), (1, 4096, True)])
 def test_block_front_streaming_kernels_f32(n, rps, drop):
+    front_case_f32(n, rps, drop, 1, 1)
+
+
+def front_case_f32(n, rps, drop, mode1, mode2):
     """csrc/pointwise.hip, fp32 family: the front of a residual block (bn1 -> relu -> conv1 1x1 at 64 channels -> Dropout2d ->
     bn2 -> relu) without ever writing d1 -- statistics pass, a2 pass, fused backward -- against the emulation and against the
-    HIP ops they replace (conv_fwd + bn_relu_apply / bn_bwd_apply + conv_dgrad + conv_wgrad)"""
+    HIP ops they replace (conv_fwd + bn_relu_apply / bn_bwd_apply + conv_dgrad + conv_wgrad).
+    mode1 / mode2: batch (1) or running (2) statistics in bn1 / bn2 -- (2, 2) is a backward pass taken in eval mode
+    (tests/test_bn_modes_gpu.py runs the modes beside (1, 1))."""
     c, rows = 64, n * rps
-    gen = torch.Generator().manual_seed(n * 1000 + rps)
+    gen = torch.Generator().manual_seed(n * 1000 + rps + 10 * mode1 + 100 * mode2 - 110)
     x = torch.randn(n, rps, 1, c, generator=gen)
     w1 = torch.randn(1, c, c, generator=gen) / 8
     bias = 0.1 * torch.randn(c, generator=gen)
-    bn1 = make_bn(c, rows, 1, gen, x)
+    bn1 = make_bn(c, rows, mode1, gen, x if mode1 == 1 else None)
     mask = Mask((torch.rand(n, c, generator=gen) < 0.5).float() * 2, 1, rps) if drop else None
     g1 = Geom(n, rps, 1, rps, 1, c, c, 1, 1, 1, 1, 0, 0, False)
     xd, wd, bd, bn1d, md = x.to(DEV), w1.to(DEV), bias.to(DEV), to_dev(bn1), to_dev(mask)
@@ -676,6 +683,11 @@ def test_block_front_streaming_kernels_f32(n, rps, drop):
     d1_old = ops.conv_fwd(xd, wd, g1, bn_in=bn1d, bias=bd, mask=md, out_stats=st_old)
     check("front32/stats_vs_conv_fwd", st, st_old, rtol=1e-4, atol_rel=1e-4)
     bn2 = Bn(torch.rand(c, generator=gen) + 0.5, 0.1 * torch.randn(c, generator=gen), 1, st_ref.clone(), rows)
+    if mode2 == 2:      # running statistics near d1's own, as a trained model's are
+        mean_d1 = (st_ref[0] / rows).float()
+        var_d1 = (st_ref[1] / rows).float() - mean_d1 * mean_d1
+        bn2 = Bn(bn2.gamma, bn2.beta, 2, rmean=mean_d1 + 0.1 * torch.randn(c, generator=gen),
+                 rvar=var_d1 * (0.75 + 0.5 * torch.rand(c, generator=gen)))
     bn2d = to_dev(bn2)
     a2_ref = TB.block_front_apply(x, w1, bias, bn1, bn2, mask)
     a2 = ops.block_front_apply(xd, wd, bd, bn1d, bn2d, md)
@@ -704,6 +716,17 @@ def test_block_front_streaming_kernels_f32(n, rps, drop):
     check("front32/dh1_vs_old_ops", dh1, dh1_old)
     check("front32/sums1_vs_old_ops", s1, s1_old, rtol=5e-4, atol_rel=5e-4)
     check("front32/dw1_vs_old_ops", dw, ops.conv_wgrad(xd, dc1_old, g1, bn_in=bn1d), rtol=5e-4, atol_rel=5e-4)
+    if (mode1, mode2) != (1, 1):
+        # conv2's input gradient with its ReLU mask / x-hat taken from a2 (bn mode 3: gamma and beta alone, no sums) == from
+        # d1 (bn2 itself), as the bf16 family's test: the fp32 forward front (MOPOE_BLOCK_FRONT_F32_FWD=1) leaves no d1 either
+        g2 = Geom(n, 1, rps // 2, 1, rps, c, 128, 1, 4, 1, 2, 0, 1, False)
+        w2 = (torch.randn(g2.taps, c, 128, generator=gen) / 16).to(DEV)
+        dm = torch.randn(g2.out_shape, generator=gen).to(DEV)
+        sa, sb = torch.zeros(2, c, dtype=torch.float64, device=DEV), torch.zeros(2, c, dtype=torch.float64, device=DEV)
+        ga = ops.conv_dgrad(dm, w2, g2, relu_bn=bn2d, xin=d1_old.view(g2.in_shape), bwd_sums=sa)
+        gb = ops.conv_dgrad(dm, w2, g2, relu_bn=Bn(bn2d.gamma, bn2d.beta, 3), xin=a2.view(g2.in_shape), bwd_sums=sb)
+        check("front32/conv2_dgrad_mask_from_a2", gb, ga)
+        check("front32/conv2_dgrad_sums_from_a2", sb, sa, rtol=2e-4, atol_rel=2e-4)
 
 
 @pytest.mark.parametrize("b,L,V", [(4, 128, 3520), (3, 7, 64), (2, 5, 8), (1, 3, 5000), (2, 4, 10240)])
