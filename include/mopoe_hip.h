@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MOPOE_ABI_VERSION 24
+#define MOPOE_ABI_VERSION 25
 
 /* error codes */
 #define MOPOE_OK 0
@@ -546,7 +546,9 @@ int mopoe_embedding_bwd_bf16(const float* ids, const uint16_t* gout, float* dtab
  * the updated parameter is written in the same pass (the bf16 family's MFMA operands).
  * step: device scalar (float), incremented first (NULL: a further part of a step whose counter and coefficients an
  * earlier call with nseg >= 0 has already set in `coef`: the tensors of one step may be updated by several calls).  lr_dev: device scalar or NULL (then `lr`).  coef: float[2] device scratch.
- * The hyper-parameters are doubles, as in optim.Adam: 1 - beta2 formed from the float 0.999 is off by 1.3e-5 relative. */
+ * The hyper-parameters are doubles, as in optim.Adam: 1 - beta2 formed from the float 0.999 is off by 1.3e-5 relative.
+ * The global gradient-norm clip in front of this step (--max_grad_norm: the norm over the same records, and this step
+ * under the scale / skip decision it leaves on the device) has its own header, include/mopoe_hip_optim.h. */
 typedef struct {
   float* p;
   const float* g;

@@ -142,7 +142,8 @@ def parse_flags(argv=None) -> argparse.Namespace:
 
 def result_line(history) -> dict:
     """the launcher's final JSON line; 'last_lhoods' only when --calc_nll computed an estimate, 'last_lr_eval' only when
-    --eval_lr evaluated the latent representation"""
+    --eval_lr evaluated the latent representation, 'last_grad_norm' (the last train step's norm before clipping) and
+    'skipped_steps' (updates skipped for a non-finite norm, whole run) only with --max_grad_norm"""
     last = history[-1]
     result = {"epochs": len(history), "last_test_loss": last["test"].get("total_loss"),
               "graphed_steps_last_epoch": last["train"].get("graphed_steps")}
@@ -152,6 +153,10 @@ def result_line(history) -> dict:
     lr_evals = [h["test"]["lr_eval"] for h in history if "lr_eval" in h["test"]]
     if lr_evals:
         result["last_lr_eval"] = lr_evals[-1]
+    last_step = last["train"].get("last", {})
+    if "grad_norm" in last_step:
+        result["last_grad_norm"] = last_step["grad_norm"]
+        result["skipped_steps"] = int(last_step.get("skipped_steps", 0))
     return result
 
 

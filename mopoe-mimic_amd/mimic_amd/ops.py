@@ -21,7 +21,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOPOE_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libmopoe_hip.so")  # env override: A/B builds
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 RES_A, RES_B = 2.0, 0.3
 BN_EPS = 1e-5
@@ -934,11 +934,54 @@ def stamp(name):
     _check(lib().mopoe_prof_stamp(C.c_void_p(st["buf"].data_ptr() + 8 * i), _stream()))
 
 
-def adam_step(params, grads, ms, vs, step, lr, beta1, beta2, eps, coef, lowp=None, prep=True):
+CLIP_NORM, CLIP_SCALE, CLIP_SKIP, CLIP_SKIPPED_TOTAL, CLIP_STATE_LEN = 0, 1, 2, 3, 4   # include/mopoe_hip_optim.h: the clip state
+GRAD_NORM_CHUNK = 4096     # elements per partial sum (csrc/adam.hip: ADAM_CHUNK)
+
+
+def grad_norm_partials(numels) -> int:
+    """doubles of scratch that suffice for grad_norm over tensors of these sizes, whichever of them have a gradient
+    (header: mopoe_grad_norm_partials)"""
+    n = len(numels)
+    arr = (_AdamSeg * n)()
+    for i, k in enumerate(numels):
+        arr[i] = _AdamSeg(None, None, None, None, None, int(k))
+    fn = lib().mopoe_grad_norm_partials
+    fn.restype = C.c_int64
+    count = int(fn(arr, n))
+    if count < 0:
+        _check(count)
+    return count
+
+
+def grad_norm(grads, max_norm, state, scratch):
+    """The global L2 norm of all gradients and the clip decision it implies (header: mopoe_grad_norm), deterministic and
+    without a host sync.  grads: list of fp32 tensors (None entries contribute nothing); state: float32 [4] on the device,
+    left as {norm before clipping, scale = min(1, max_norm / (norm + 1e-6)), skip (1 if the norm is not finite),
+    skipped_total += skip}; scratch: float64 [>= grad_norm_partials(sizes)].  Returns state (adam_step's clip=)."""
+    if state.dtype != torch.float32 or state.numel() != CLIP_STATE_LEN or scratch.dtype != torch.float64:
+        raise MopoeHipError("grad_norm: state is float32 [4], scratch is float64")
+    _dev(state, scratch)
+    n = len(grads)
+    arr = (_AdamSeg * n)()
+    for i, g_ in enumerate(grads):
+        if g_ is None:
+            arr[i] = _AdamSeg(None, None, None, None, None, 0)
+            continue
+        if g_.dtype != torch.float32:
+            raise MopoeHipError("grad_norm: gradients must be fp32 tensors")
+        _dev(g_)
+        arr[i] = _AdamSeg(None, g_.data_ptr(), None, None, None, g_.numel())
+    _check(lib().mopoe_grad_norm(arr, n, C.c_double(float(max_norm)), _p(scratch), C.c_int64(scratch.numel()), _p(state),
+                                 _stream()))
+    return state
+
+
+def adam_step(params, grads, ms, vs, step, lr, beta1, beta2, eps, coef, lowp=None, prep=True, clip=None):
     """One Adam step over all tensors (header: mopoe_adam_step).  params / grads / ms / vs: equally long lists of fp32
     tensors (a grad may be None: that tensor is skipped, like optim.Adam does); step: device scalar (float), incremented;
     lr: float or device scalar; coef: float[2] device scratch; lowp: optional list of bf16 copies (or None entries)
-    rewritten in the same pass."""
+    rewritten in the same pass.  clip: the state grad_norm left (header: mopoe_adam_step_clipped): every gradient is
+    multiplied by its scale as it is loaded, and nothing at all is written -- step and coef included -- when it says skip."""
     n = len(params)
     arr = (_AdamSeg * n)()
     for i in range(n):
@@ -953,6 +996,14 @@ def adam_step(params, grads, ms, vs, step, lr, beta1, beta2, eps, coef, lowp=Non
         arr[i] = _AdamSeg(p_.data_ptr(), g_.data_ptr(), ms[i].data_ptr(), vs[i].data_ptr(),
                           None if lp is None else lp.data_ptr(), p_.numel())
     lr_dev = lr if isinstance(lr, torch.Tensor) else None
+    if clip is not None:
+        if clip.dtype != torch.float32 or clip.numel() != CLIP_STATE_LEN:
+            raise MopoeHipError("adam_step: clip is the float32 [4] state of grad_norm")
+        _dev(clip)
+        _check(lib().mopoe_adam_step_clipped(arr, n, _p(step) if prep else None, _p(lr_dev),
+                                             C.c_double(0.0 if lr_dev is not None else float(lr)), C.c_double(beta1),
+                                             C.c_double(beta2), C.c_double(eps), _p(coef), _p(clip), _stream()))
+        return
     _check(lib().mopoe_adam_step(arr, n, _p(step) if prep else None, _p(lr_dev), C.c_double(0.0 if lr_dev is not None else float(lr)),
                                  C.c_double(beta1), C.c_double(beta2), C.c_double(eps), _p(coef), _stream()))
 

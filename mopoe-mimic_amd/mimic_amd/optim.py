@@ -13,7 +13,20 @@ tensor without a gradient is skipped (its moments stay) but the shared counter a
 gradient-less parameters is fixed for a run (the word encoder's unused resblock_7/8): those are never updated by either
 optimiser, and `check_uniform_grads` raises the first time a parameter's has-gradient state CHANGES between steps.
 early_begin() advances the counter before the backward: a backward that raises leaves the counter one ahead with no
-update applied (the run is over at that point: OOM -> new process, main_mimic.Main)."""
+update applied (the run is over at that point: OOM -> new process, main_mimic.Main).
+
+max_grad_norm > 0 (--max_grad_norm): step() clips the GLOBAL gradient norm in front of the update, with the semantics of
+torch.nn.utils.clip_grad_norm_(params, max_grad_norm, norm_type=2): total_norm = sqrt(sum of g^2) over every parameter that
+has a gradient, scale = min(1, max_grad_norm / (total_norm + 1e-6)), the update uses scale * g.  Norm, scale and update are
+device work on fixed buffers (ops.grad_norm, ops.adam_step(clip=...)): capturable, deterministic, and behind a gradient
+all-reduce the norm is that of the reduced gradients, the same on every rank.  Two deliberate differences from torch:
+  1. p.grad is NOT rewritten: the scale is applied where the Adam kernel loads the gradient (one read and one write of all
+     gradients saved per step).  clip_state[0], the `grad_norm` the train loop reports, is the norm BEFORE clipping, as
+     torch's return value is.
+  2. a total_norm that is not finite SKIPS the update on the device: no parameter, moment, bf16 weight copy or step counter
+     changes, and clip_state[3] (skipped steps) goes up by one.  torch would multiply every gradient by NaN.
+The global norm needs every gradient, so the per-network early updates (early_begin / early_step) are not available while
+clipping: run_epochs.train_step does not arm them, and early_begin() raises."""
 from __future__ import annotations
 
 import torch
@@ -22,8 +35,11 @@ from . import ops
 
 
 class HipAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0):
         params = [p for p in params]
+        max_grad_norm = float(max_grad_norm)
+        if not (0.0 <= max_grad_norm < float("inf")):
+            raise ValueError(f"HipAdam: max_grad_norm must be finite and >= 0 (0 = no clipping), got {max_grad_norm}")
         if not params or not all(p.dtype == torch.float32 for p in params):
             raise ValueError("HipAdam needs fp32 parameters (on the GPU: ops.adam_step has no CPU fallback)")
         dev = params[0].device
@@ -50,13 +66,22 @@ class HipAdam(torch.optim.Optimizer):
         self._held = None      # an in-line network's update waiting for the next in-line network
         for p, m, v in zip(self._params, self._m, self._v):
             self.state[p] = dict(step=self._step, exp_avg=m.view_as(p), exp_avg_sq=v.view_as(p))
+        # gradient-norm clip: state {norm, scale, skip, skipped steps} and the partial sums, allocated once (a capture
+        # bakes their addresses into its nodes); None = no clipping, and step() is exactly the unclipped one
+        self.max_grad_norm = max_grad_norm
+        self.clip_state = self._clip_scratch = None
+        if max_grad_norm > 0:
+            self.clip_state = torch.zeros(ops.CLIP_STATE_LEN, dtype=torch.float32, device=dev)
+            n_partials = ops.grad_norm_partials([p.numel() for p in self._params])
+            self._clip_scratch = torch.zeros(max(n_partials, 1), dtype=torch.float64, device=dev)
 
     def _launch(self, idx, grads, prep):
         group = self.param_groups[0]
         b1, b2 = group["betas"]
         pick = lambda xs: [xs[i] for i in idx]
         ops.adam_step(pick(self._params), grads, pick(self._m), pick(self._v), self._step, group["lr"], b1, b2, group["eps"],
-                      self._coef, lowp=None if self.lowp is None else pick(self.lowp), prep=prep)
+                      self._coef, lowp=None if self.lowp is None else pick(self.lowp), prep=prep,
+                      **({} if self.clip_state is None else {"clip": self.clip_state}))
 
     def check_uniform_grads(self):
         """eager steps only (host-side, no device work): the has-gradient pattern must not change between steps (see the
@@ -74,6 +99,9 @@ class HipAdam(torch.optim.Optimizer):
     def early_begin(self):
         """a step in parts: advance the step counter now (current stream); early_step() then updates tensors whose gradients
         are final while the rest of the backward still runs, step() the remaining ones"""
+        if self.clip_state is not None:
+            raise RuntimeError("HipAdam: early per-network updates cannot be combined with max_grad_norm (the global norm "
+                               "needs every gradient)")
         self._launch([], [], True)
         self._early, self._held = set(), None
 
@@ -122,6 +150,8 @@ class HipAdam(torch.optim.Optimizer):
                 g = g.contiguous()
             idx.append(i)
             grads.append(g)
+        if self.clip_state is not None:       # (early is None here: every parameter is in idx)
+            ops.grad_norm(grads, self.max_grad_norm, self.clip_state, self._clip_scratch)
         if early is None or any(g is not None for g in grads):
             self._launch(idx, grads, early is None)
         return loss

@@ -86,7 +86,9 @@ class ScalarPack:
         self.names: typing.List[str] = []
         self.static = None     # the captured device-side pack of a GraphedTrainStep
 
-    def submit(self, routine, reducer: typing.Optional["GradAllReducer"] = None):
+    def submit(self, routine, reducer: typing.Optional["GradAllReducer"] = None, clip_state=None):
+        """clip_state: optim.HipAdam.clip_state of a clipping optimiser whose step is already enqueued (None: no clipping,
+        and the pack is the 18 scalars above): two more names, `grad_norm` (before clipping) and `skipped_steps`"""
         res = routine["results"]
         names, vals = ["total_loss", "joint_divergence"], [routine["total_loss"].detach().reshape(1),
                                                            res["joint_divergence"].detach().reshape(1)]
@@ -109,6 +111,9 @@ class ScalarPack:
             vals.append(torch.stack(lat).mean(dim=(1, 2)))
         elif lat:   # (style latents of other widths: one mean per tensor)
             vals.append(torch.stack([t.mean() for t in lat]))
+        if clip_state is not None:   # (data parallel: the norm of the reduced gradients, equal on every rank)
+            names += ["grad_norm", "skipped_steps"]
+            vals += [clip_state[0:1], clip_state[3:4]]
         packed = torch.cat(vals)
         self.names = names
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
@@ -148,7 +153,8 @@ def train_step(exp, batch, reducer=None, pack: typing.Optional[ScalarPack] = Non
     """One optimiser step of run_epochs.train (:122-131)."""
     routine = basic_routine_epoch(exp, batch)
     exp.optimizer.zero_grad(set_to_none=True)
-    early = EARLY_ADAM and reducer is None and hasattr(exp.optimizer, "early_begin")
+    clip_state = getattr(exp.optimizer, "clip_state", None)    # (--max_grad_norm: the global norm needs every gradient)
+    early = EARLY_ADAM and reducer is None and hasattr(exp.optimizer, "early_begin") and clip_state is None
     if early:   # every network's parameters are updated on its own stream as soon as its backward is enqueued
         from . import nets as _nets
         exp.optimizer.early_begin()
@@ -164,14 +170,16 @@ def train_step(exp, batch, reducer=None, pack: typing.Optional[ScalarPack] = Non
     exp.optimizer.step()
     note_params_changed()
     if pack is not None:
-        pack.submit(routine, reducer)
+        pack.submit(routine, reducer, clip_state)
     return routine
 
 
 # Each network's parameters are updated (optim.HipAdam.early_step) on the network's own stream right behind its backward
 # instead of all together after the last backward: the update of 53 of the 65 M parameters then runs beside the image
 # encoders' backward, and only a 30-us remainder follows the join (C2 +1.0 %, C5 +1.4 %, C3 +0.3 %).  Not with a gradient
-# reducer (the gradients must be averaged first).  MOPOE_EARLY_ADAM=0: one optimiser step after the backward.
+# reducer (the gradients must be averaged first) and not with --max_grad_norm (the global norm needs every gradient: norm,
+# then one clipped update of all parameters, behind the backward -- and, data parallel, behind the all-reduce).
+# MOPOE_EARLY_ADAM=0: one optimiser step after the backward.
 EARLY_ADAM = os.environ.get("MOPOE_EARLY_ADAM", "1") == "1"
 
 
@@ -292,7 +300,7 @@ class GraphedTrainStep:
             self.reducer.finish_static(early + late)
             self.graph_opt.replay()
             if self.pack is not None:
-                self.pack.submit(self.routine, self.reducer)
+                self.pack.submit(self.routine, self.reducer, getattr(self.exp.optimizer, "clip_state", None))
         elif self.pack is not None:   # the captured step packed its scalars on the device: copy them out
             self.pack.flush()
         for m, d in self._bn_bump:

@@ -39,6 +39,9 @@ def default_flags(**overrides) -> argparse.Namespace:
         start_epoch=0, end_epoch=1, eval_freq=10, world_size=1, dataloader_workers=0, weighted_sampler=False,
         dir_data=".", word_min_occ=3, undersample_dataset=False, binary_labels=False,   # real tensor datasets (dataio.Mimic)
         compute_dtype="fp32",   # 'bf16': bf16 storage + bf16 MFMA with fp32 accumulation (BASELINE configs #3, #5)
+        # > 0: optim.HipAdam clips the global gradient norm to this value on the device, inside the (captured) step, and skips
+        # the update of a step whose norm is not finite; 0 = no clipping (the reference has none)
+        max_grad_norm=0.0,
         mm_vae_save="mm_vae", start_early_stopping_epoch=0, max_early_stopping_index=5, testing_batches=2,
         encoder_save_m1="encoderM1", encoder_save_m2="encoderM2", encoder_save_m3="encoderM3",
         decoder_save_m1="decoderM1", decoder_save_m2="decoderM2", decoder_save_m3="decoderM3",
@@ -57,6 +60,12 @@ def check_flags(flags):
     if getattr(flags, "calc_nll", False) and getattr(flags, "factorized_representation", False):
         from ..evaluation.eval_metrics.likelihood import check_style_dims
         check_style_dims(flags)
+    max_grad_norm = float(getattr(flags, "max_grad_norm", 0.0))
+    if not (0.0 <= max_grad_norm < float("inf")):
+        raise ValueError(f"--max_grad_norm must be finite and >= 0 (0 = no clipping), got {max_grad_norm}")
+    if max_grad_norm > 0 and os.environ.get("MOPOE_TORCH_ADAM", "0") == "1":
+        raise ValueError("--max_grad_norm clips inside mimic_amd.optim.HipAdam; MOPOE_TORCH_ADAM=1 replaces that optimiser "
+                         "with PyTorch's Adam (an A/B aid, not a training mode): use one or the other")
     if getattr(flags, "weighted_sampler", False) and getattr(flags, "dataset", None) == "testing":
         raise ValueError("--weighted_sampler weights the training rows by their labels: dataset='testing' (the synthetic "
                          "Mimic_testing) has no label table; use it with the tensor files of --dir_data")
@@ -129,9 +138,16 @@ class HotPathExperiment:
         lr = self.flags.initial_learning_rate
         betas = (self.flags.beta_1, self.flags.beta_2)
         shadows = [m._shadow for m in self.mm_vae.modules() if getattr(m, "_shadow", None) is not None]
+        max_grad_norm = float(getattr(self.flags, "max_grad_norm", 0.0))
+        if max_grad_norm > 0 and os.environ.get("MOPOE_TORCH_ADAM", "0") == "1":
+            raise ValueError("--max_grad_norm clips inside mimic_amd.optim.HipAdam; MOPOE_TORCH_ADAM=1 replaces that "
+                             "optimiser with PyTorch's Adam: use one or the other")
         if capturable and os.environ.get("MOPOE_TORCH_ADAM", "0") != "1":
             self.set_hip_adam(params, lr, betas, shadows)
             return
+        if max_grad_norm > 0:
+            raise ValueError("--max_grad_norm needs mimic_amd.optim.HipAdam (parameters on the GPU, a capturable "
+                             "optimiser); PyTorch's Adam would silently train without the clip")
         for sh in shadows:
             sh.bind_optimizer(False)
         if capturable:
@@ -140,7 +156,8 @@ class HotPathExperiment:
 
     def set_hip_adam(self, params, lr, betas, shadows):
         from ..optim import HipAdam
-        self.optimizer = HipAdam([p for p in params if p.requires_grad], lr=lr, betas=betas)
+        self.optimizer = HipAdam([p for p in params if p.requires_grad], lr=lr, betas=betas,
+                                 max_grad_norm=float(getattr(self.flags, "max_grad_norm", 0.0)))
         # bf16 family: the kernel that updates a master weight also rewrites its bf16 copy (no cast pass per step)
         lowp = {}
         for sh in shadows:
