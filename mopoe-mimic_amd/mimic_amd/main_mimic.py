@@ -143,7 +143,8 @@ def parse_flags(argv=None) -> argparse.Namespace:
 def result_line(history) -> dict:
     """the launcher's final JSON line; 'last_lhoods' only when --calc_nll computed an estimate, 'last_lr_eval' only when
     --eval_lr evaluated the latent representation, 'last_grad_norm' (the last train step's norm before clipping) and
-    'skipped_steps' (updates skipped for a non-finite norm, whole run) only with --max_grad_norm"""
+    'skipped_steps' (updates skipped for a non-finite norm, whole run) only with --max_grad_norm, 'eval_weights' ('ema':
+    the test pass and the evaluation hooks ran on the averaged weights) only with --ema_decay"""
     last = history[-1]
     result = {"epochs": len(history), "last_test_loss": last["test"].get("total_loss"),
               "graphed_steps_last_epoch": last["train"].get("graphed_steps")}
@@ -157,6 +158,8 @@ def result_line(history) -> dict:
     if "grad_norm" in last_step:
         result["last_grad_norm"] = last_step["grad_norm"]
         result["skipped_steps"] = int(last_step.get("skipped_steps", 0))
+    if "weights" in last["test"]:
+        result["eval_weights"] = last["test"]["weights"]
     return result
 
 

@@ -64,6 +64,10 @@ class _AdamSeg(C.Structure):
                 ("n", C.c_int64)]
 
 
+class _EmaSeg(C.Structure):   # mopoe_ema_seg (include/mopoe_hip_ema.h)
+    _fields_ = [("p", C.c_void_p), ("ema", C.c_void_p), ("p16", C.c_void_p), ("n", C.c_int64)]
+
+
 @dataclass(frozen=True)
 class Geom:
     """Conv / ConvTranspose geometry; 'small' grid = conv output / convT input (header: mopoe_conv_geom)."""
@@ -1006,6 +1010,43 @@ def adam_step(params, grads, ms, vs, step, lr, beta1, beta2, eps, coef, lowp=Non
         return
     _check(lib().mopoe_adam_step(arr, n, _p(step) if prep else None, _p(lr_dev), C.c_double(0.0 if lr_dev is not None else float(lr)),
                                  C.c_double(beta1), C.c_double(beta2), C.c_double(eps), _p(coef), _stream()))
+
+
+def _ema_records(who, params, emas, lowp=None):
+    n = len(params)
+    arr = (_EmaSeg * n)()
+    for i in range(n):
+        p_, e_ = params[i], emas[i]
+        if p_.dtype != torch.float32 or e_.dtype != torch.float32 or e_.numel() != p_.numel():
+            raise MopoeHipError(f"{who}: parameters and averages must be fp32 tensors of equal size")
+        lp = lowp[i] if lowp is not None else None
+        if lp is not None and (lp.dtype != torch.bfloat16 or lp.numel() != p_.numel()):
+            raise MopoeHipError(f"{who}: a low-precision copy must be a bf16 tensor of its parameter's size")
+        _dev(p_, e_, lp)
+        arr[i] = _EmaSeg(p_.data_ptr(), e_.data_ptr(), None if lp is None else lp.data_ptr(), p_.numel())
+    return arr, n
+
+
+def ema_update(params, emas, decay, step, clip=None):
+    """ema += w * (p - ema) over all tensors (header: mopoe_ema_update), w = 1 - min(decay, (1 + step) / (10 + step)) formed
+    on the device from `step`, Adam's device step counter after this step's increment.  params / emas: equally long lists
+    of fp32 tensors; clip: the state grad_norm left -- nothing at all is written when it says the step was skipped."""
+    arr, n = _ema_records("ema_update", params, emas)
+    if step.dtype != torch.float32:
+        raise MopoeHipError("ema_update: step is Adam's float32 device step counter")
+    _dev(step)
+    if clip is not None:
+        if clip.dtype != torch.float32 or clip.numel() != CLIP_STATE_LEN:
+            raise MopoeHipError("ema_update: clip is the float32 [4] state of grad_norm")
+        _dev(clip)
+    _check(lib().mopoe_ema_update(arr, n, C.c_double(float(decay)), _p(step), _p(clip), _stream()))
+
+
+def ema_swap(params, emas, lowp=None):
+    """Exchange every parameter with its average in place, bit for bit (header: mopoe_ema_swap); lowp: optional list of
+    bf16 copies (or None entries), rewritten from the values the parameters then hold."""
+    arr, n = _ema_records("ema_swap", params, emas, lowp)
+    _check(lib().mopoe_ema_swap(arr, n, _stream()))
 
 
 def colsum(x, out=None):

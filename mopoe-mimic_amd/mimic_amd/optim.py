@@ -26,7 +26,20 @@ all-reduce the norm is that of the reduced gradients, the same on every rank.  T
   2. a total_norm that is not finite SKIPS the update on the device: no parameter, moment, bf16 weight copy or step counter
      changes, and clip_state[3] (skipped steps) goes up by one.  torch would multiply every gradient by NaN.
 The global norm needs every gradient, so the per-network early updates (early_begin / early_step) are not available while
-clipping: run_epochs.train_step does not arm them, and early_begin() raises."""
+clipping: run_epochs.train_step does not arm them, and early_begin() raises.
+
+ema_decay > 0 (--ema_decay): an exponential moving average of every parameter, one flat fp32 allocation at the moments'
+offsets, initialised from the parameters when the optimiser is built (a caller that loads weights into the model AFTER that
+must call reset_ema() itself: nothing here does it for it, and the average would silently go on from the old weights).  _launch() enqueues
+ops.ema_update right behind each ops.adam_step, on the same stream and over the same tensors (those that have a gradient),
+so one hook serves the eager step, the captured one, the per-network early updates (a network's average is updated on that
+network's lane), the clipped step (a skipped step does not move the average: the kernel reads clip_state) and the
+data-parallel optimiser graph.  The decay warms up on the device from the shared step counter:
+d = min(ema_decay, (1 + step) / (10 + step)).  A parameter that never receives a gradient keeps an average equal to itself.
+swap_ema() exchanges parameters and averages IN PLACE (a captured step has the parameter addresses in its nodes), rewrites
+the bf16 weight copies of self.lowp from the values swapped in, and flips a host flag; while it is set, step(),
+early_begin() and early_step() raise: training on swapped-in weights would corrupt both sets.  BatchNorm buffers are not
+averaged, and the average is not part of state_dict() (a resumed run starts a new average from the loaded weights)."""
 from __future__ import annotations
 
 import torch
@@ -35,9 +48,12 @@ from . import ops
 
 
 class HipAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, ema_decay=0.0):
         params = [p for p in params]
         max_grad_norm = float(max_grad_norm)
+        ema_decay = float(ema_decay)
+        if not (0.0 <= ema_decay < 1.0):
+            raise ValueError(f"HipAdam: ema_decay must be finite and in [0, 1) (0 = no average), got {ema_decay}")
         if not (0.0 <= max_grad_norm < float("inf")):
             raise ValueError(f"HipAdam: max_grad_norm must be finite and >= 0 (0 = no clipping), got {max_grad_norm}")
         if not params or not all(p.dtype == torch.float32 for p in params):
@@ -74,6 +90,15 @@ class HipAdam(torch.optim.Optimizer):
             self.clip_state = torch.zeros(ops.CLIP_STATE_LEN, dtype=torch.float32, device=dev)
             n_partials = ops.grad_norm_partials([p.numel() for p in self._params])
             self._clip_scratch = torch.zeros(max(n_partials, 1), dtype=torch.float64, device=dev)
+        # weight average: one flat allocation at the moments' offsets (a capture bakes its addresses into its nodes); None =
+        # no average, and no launch of step() differs from today's
+        self.ema_decay = ema_decay
+        self._ema_flat = self._ema = None
+        self._swapped = False   # swap_ema(): the parameters hold the average, the average holds the live weights
+        if ema_decay > 0:
+            self._ema_flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+            self._ema = [self._ema_flat[o:o + p.numel()] for o, p in zip(offs, self._params)]
+            self.reset_ema()
 
     def _launch(self, idx, grads, prep):
         group = self.param_groups[0]
@@ -82,6 +107,53 @@ class HipAdam(torch.optim.Optimizer):
         ops.adam_step(pick(self._params), grads, pick(self._m), pick(self._v), self._step, group["lr"], b1, b2, group["eps"],
                       self._coef, lowp=None if self.lowp is None else pick(self.lowp), prep=prep,
                       **({} if self.clip_state is None else {"clip": self.clip_state}))
+        if self._ema is not None:
+            # right behind the Adam launch that wrote these tensors, on its stream; the step counter is the incremented one
+            live = [i for i, g in zip(idx, grads) if g is not None]
+            if live:
+                ops.ema_update([self._params[i] for i in live], [self._ema[i] for i in live], self.ema_decay, self._step,
+                               clip=self.clip_state)
+
+    # ---- the weight average (ema_decay > 0) -------------------------------------------------------------------------
+    def _need_ema(self, what):
+        if self._ema is None:
+            raise RuntimeError(f"HipAdam.{what}: no weight average is kept (ema_decay is 0)")
+
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"HipAdam.{what}: the averaged weights are swapped in (swap_ema()); training on them would "
+                               "corrupt both the live weights and the average -- swap back first")
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """average = parameters.  Called at construction.  Nothing in the package loads weights into the model after the
+        optimiser is built; code that does (a resume path) MUST call this afterwards itself, or the average goes on from the
+        weights the optimiser was built on -- no launch can notice that."""
+        self._need_ema("reset_ema")
+        self._not_swapped("reset_ema")
+        for e, p in zip(self._ema, self._params):
+            e.copy_(p.detach().reshape(-1))
+
+    def ema_tensors(self):
+        """views of the average shaped like the parameters, in their order (while swapped: the live weights)"""
+        self._need_ema("ema_tensors")
+        return [e.view_as(p) for e, p in zip(self._ema, self._params)]
+
+    @property
+    def ema_swapped(self) -> bool:
+        return self._swapped
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """exchange every parameter with its average in place (current stream), the bf16 weight copies rewritten from the
+        values swapped in (layout.Bf16Weights under synced_by_optimizer only watches the tensors' version counters, which a
+        library launch does not move); layout.note_params_changed() makes eval-mode copies (the padded vocabulary head)
+        refresh.  A second call restores every bit."""
+        from .layout import note_params_changed
+        self._need_ema("swap_ema")
+        ops.ema_swap(self._params, self._ema, lowp=self.lowp)
+        note_params_changed()
+        self._swapped = not self._swapped
 
     def check_uniform_grads(self):
         """eager steps only (host-side, no device work): the has-gradient pattern must not change between steps (see the
@@ -99,6 +171,7 @@ class HipAdam(torch.optim.Optimizer):
     def early_begin(self):
         """a step in parts: advance the step counter now (current stream); early_step() then updates tensors whose gradients
         are final while the rest of the backward still runs, step() the remaining ones"""
+        self._not_swapped("early_begin")
         if self.clip_state is not None:
             raise RuntimeError("HipAdam: early per-network updates cannot be combined with max_grad_norm (the global norm "
                                "needs every gradient)")
@@ -110,6 +183,7 @@ class HipAdam(torch.optim.Optimizer):
         """inline: the network ran on the caller's stream, where the next phase of the backward is waiting behind it (the
         text decoder in front of the latent node): its update is held back until the next in-line network is done (the
         text encoder, behind which the caller's stream only waits for the other lanes) or until step()."""
+        self._not_swapped("early_step")
         idx, gs = [], []
         for p, g in zip(params, grads):
             i = self._index.get(id(p))
@@ -131,6 +205,7 @@ class HipAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._not_swapped("step")
         loss = None
         if closure is not None:
             with torch.enable_grad():

@@ -536,6 +536,13 @@ class Callbacks:
             os.makedirs(dir_network_epoch, exist_ok=True)
             self.exp.mm_vae.save_networks()
             torch.save(self.exp.mm_vae.state_dict(), os.path.join(dir_network_epoch, getattr(f, "mm_vae_save", "mm_vae")))
+            if float(getattr(self.exp.optimizer, "ema_decay", 0.0)) > 0:
+                # --ema_decay: the same file under the averaged weights beside it (same keys and layouts, BatchNorm buffers
+                # those of the live model); cloned inside the block, because state_dict() returns views of the parameters
+                with self.exp.averaged_weights():
+                    live = self.exp.mm_vae.state_dict()
+                    averaged = type(live)((k, v.detach().clone()) for k, v in live.items())
+                torch.save(averaged, os.path.join(dir_network_epoch, getattr(f, "mm_vae_save", "mm_vae") + "_ema"))
 
 
 def _rank_of(device) -> int:
@@ -608,13 +615,19 @@ def run_epochs(rank, exp) -> typing.List[dict]:
             tr = train(exp, PrefetchToDevice(train_loader, args.device), reducer)
         if reducer is not None:
             reducer.sync_buffers()       # running statistics are per rank during training; rank 0's are evaluated / saved
-        test_results = test(epoch, exp, test_loader if resident else PrefetchToDevice(test_loader, args.device))
-        if getattr(args, "eval_lr", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
-            test_results["lr_eval"] = evaluate_latent_representation(exp, epoch)
-        if getattr(args, "calc_nll", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
-            lhoods = estimate_test_likelihoods(exp, epoch)
-            if lhoods is not None:
-                test_results["lhoods"] = lhoods
+        # --ema_decay: the whole evaluation of the epoch sees the averaged weights (swapped in place, swapped back on the way
+        # out), so the plateau scheduler and early stopping below follow the averaged model's test loss; BatchNorm running
+        # statistics are the live model's.  Without an average the block changes nothing.
+        with exp.averaged_weights() as averaged:
+            test_results = test(epoch, exp, test_loader if resident else PrefetchToDevice(test_loader, args.device))
+            if getattr(args, "eval_lr", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
+                test_results["lr_eval"] = evaluate_latent_representation(exp, epoch)
+            if getattr(args, "calc_nll", False) and ((epoch + 1) % args.eval_freq == 0 or (epoch + 1) == args.end_epoch):
+                lhoods = estimate_test_likelihoods(exp, epoch)
+                if lhoods is not None:
+                    test_results["lhoods"] = lhoods
+        if averaged:
+            test_results["weights"] = "ema"
         history.append({"epoch": epoch, "train": tr, "test": test_results, "seconds": time.time() - end})
         if callbacks.update_epoch(epoch, test_results, time.time() - end):
             break

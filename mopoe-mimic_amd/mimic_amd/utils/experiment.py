@@ -4,6 +4,7 @@ classifiers, CSV bookkeeping, fonts and plotting are outside the training step (
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 from itertools import chain, combinations
 
@@ -42,6 +43,9 @@ def default_flags(**overrides) -> argparse.Namespace:
         # > 0: optim.HipAdam clips the global gradient norm to this value on the device, inside the (captured) step, and skips
         # the update of a step whose norm is not finite; 0 = no clipping (the reference has none)
         max_grad_norm=0.0,
+        # > 0: optim.HipAdam keeps an exponential moving average of the weights on the device (updated inside the captured
+        # step); the epoch's evaluation runs on it and a <mm_vae_save>_ema checkpoint is written; 0 = none (the reference has none)
+        ema_decay=0.0,
         mm_vae_save="mm_vae", start_early_stopping_epoch=0, max_early_stopping_index=5, testing_batches=2,
         encoder_save_m1="encoderM1", encoder_save_m2="encoderM2", encoder_save_m3="encoderM3",
         decoder_save_m1="decoderM1", decoder_save_m2="decoderM2", decoder_save_m3="decoderM3",
@@ -66,6 +70,12 @@ def check_flags(flags):
     if max_grad_norm > 0 and os.environ.get("MOPOE_TORCH_ADAM", "0") == "1":
         raise ValueError("--max_grad_norm clips inside mimic_amd.optim.HipAdam; MOPOE_TORCH_ADAM=1 replaces that optimiser "
                          "with PyTorch's Adam (an A/B aid, not a training mode): use one or the other")
+    ema_decay = float(getattr(flags, "ema_decay", 0.0))
+    if not (0.0 <= ema_decay < 1.0):
+        raise ValueError(f"--ema_decay must be finite and in [0, 1) (0 = no weight average), got {ema_decay}")
+    if ema_decay > 0 and os.environ.get("MOPOE_TORCH_ADAM", "0") == "1":
+        raise ValueError("--ema_decay averages the weights inside mimic_amd.optim.HipAdam; MOPOE_TORCH_ADAM=1 replaces that "
+                         "optimiser with PyTorch's Adam (an A/B aid, not a training mode): use one or the other")
     if getattr(flags, "weighted_sampler", False) and getattr(flags, "dataset", None) == "testing":
         raise ValueError("--weighted_sampler weights the training rows by their labels: dataset='testing' (the synthetic "
                          "Mimic_testing) has no label table; use it with the tensor files of --dir_data")
@@ -142,12 +152,19 @@ class HotPathExperiment:
         if max_grad_norm > 0 and os.environ.get("MOPOE_TORCH_ADAM", "0") == "1":
             raise ValueError("--max_grad_norm clips inside mimic_amd.optim.HipAdam; MOPOE_TORCH_ADAM=1 replaces that "
                              "optimiser with PyTorch's Adam: use one or the other")
+        ema_decay = float(getattr(self.flags, "ema_decay", 0.0))
+        if ema_decay > 0 and os.environ.get("MOPOE_TORCH_ADAM", "0") == "1":
+            raise ValueError("--ema_decay averages the weights inside mimic_amd.optim.HipAdam; MOPOE_TORCH_ADAM=1 replaces "
+                             "that optimiser with PyTorch's Adam: use one or the other")
         if capturable and os.environ.get("MOPOE_TORCH_ADAM", "0") != "1":
             self.set_hip_adam(params, lr, betas, shadows)
             return
         if max_grad_norm > 0:
             raise ValueError("--max_grad_norm needs mimic_amd.optim.HipAdam (parameters on the GPU, a capturable "
                              "optimiser); PyTorch's Adam would silently train without the clip")
+        if ema_decay > 0:
+            raise ValueError("--ema_decay needs mimic_amd.optim.HipAdam (parameters on the GPU, a capturable optimiser); "
+                             "PyTorch's Adam would silently train without the weight average")
         for sh in shadows:
             sh.bind_optimizer(False)
         if capturable:
@@ -157,13 +174,30 @@ class HotPathExperiment:
     def set_hip_adam(self, params, lr, betas, shadows):
         from ..optim import HipAdam
         self.optimizer = HipAdam([p for p in params if p.requires_grad], lr=lr, betas=betas,
-                                 max_grad_norm=float(getattr(self.flags, "max_grad_norm", 0.0)))
+                                 max_grad_norm=float(getattr(self.flags, "max_grad_norm", 0.0)),
+                                 ema_decay=float(getattr(self.flags, "ema_decay", 0.0)))
         # bf16 family: the kernel that updates a master weight also rewrites its bf16 copy (no cast pass per step)
         lowp = {}
         for sh in shadows:
             lowp.update(sh.bind_optimizer(True))
         if lowp:
             self.optimizer.lowp = [lowp.get(id(p)) for p in self.optimizer._params]
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """--ema_decay: inside the block the model's parameters (and their bf16 copies) ARE the averaged weights
+        (optim.HipAdam.swap_ema, in place); they are swapped back on the way out, also when the body raises.  BatchNorm
+        running statistics are shared with the live model.  Nothing happens without an average (ema_decay 0, or an
+        optimiser that keeps none)."""
+        opt = self.optimizer
+        if opt is None or float(getattr(opt, "ema_decay", 0.0)) <= 0:
+            yield False
+            return
+        opt.swap_ema()
+        try:
+            yield True
+        finally:
+            opt.swap_ema()
 
     def set_rec_weights(self):
         f = self.flags
